@@ -21,8 +21,14 @@ and index checksum), inputs resident in HBM, plus — for N > 1 — the gather o
           (`--workload cfg3` runs BASELINE.json configs[2], 10000 x 2000, strong-scaled, instead.)
 
 Prints ONE JSON line (rank 0).  `roofline` is the HBM view the contract asks for (algorithmic bytes / kernel time);
-`roofline_valu` is the roofline that actually binds this integer path (see DESIGN.md §Rooflines);
-`cpu_baseline` is the oracle's tuned CPU path timed on this box's host cores on a bounded sample of the same pairs.
+`roofline_valu` is the roofline that actually binds this integer path; both come from the
+library's own events around the last timed step.
+
+A plain run sets up, warms up, times --steps steps and prints the line (`cpu_baseline` null).  `--full` adds everything
+else, outside the timed region: `cpu_baseline` (the oracle's tuned CPU path timed on this box's host cores on a bounded
+sample of the same pairs, compared with the GPU's records), oracle samples and single-handle comparisons, per-launch
+timings, the other row-per-lane kernel, the matrix-core variants and the `extra` blocks (other configurations).
+`--dump-outputs DIR` writes what the timed path returned in its last step as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -61,6 +67,40 @@ WORKLOADS = {
 
 
 _REAL_STDOUT = None
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, fields):
+    """--dump-outputs: the timed path's outputs of its last step as out_dir/<name>.npy.  `fields` maps name -> (1-D array,
+    float32 or float64); the arrays are columns of one table (one row per pair or per loop candidate), each converted to
+    a dtype that holds its values exactly.  Above 64 MB in all, a fixed seeded sample of the rows (a function of the row
+    count only) is written instead, with its row numbers as sample_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(next(iter(fields.values()))[0])
+    row_bytes = sum(np.dtype(dt).itemsize for _, dt in fields.values())
+    sel = None
+    if n * row_bytes > DUMP_LIMIT_BYTES:
+        k = DUMP_LIMIT_BYTES // (row_bytes + 8)
+        sel = np.sort(np.random.default_rng(12345).choice(n, size=k, replace=False))
+        np.save(os.path.join(out_dir, "sample_index.npy"), sel.astype(np.float64))
+    for name, (a, dt) in fields.items():
+        a = np.asarray(a)
+        np.save(os.path.join(out_dir, name + ".npy"), (a if sel is None else a[sel]).astype(dt))
+
+
+def score_fields(scores, index_checksums=None):
+    """Columns of lcm_score records (and of the per-pair index checksums of the argmin kernel) for dump_outputs."""
+    f = {"good_count": (scores["good_count"], np.float32), "min_dist": (scores["min_dist"], np.float32),
+         "n_train": (scores["n_train"], np.float32)}
+    if index_checksums is not None:
+        f["index_checksum"] = (index_checksums, np.float64)
+    return f
+
+
+def candidate_fields(cands):
+    """Columns of LoopCandidate records (lcm_all_vs_all_loops) for dump_outputs."""
+    return {"current_frame_id": (cands["current_frame_id"], np.float64), "matched_frame_id": (cands["matched_frame_id"], np.float64),
+            "num_matches": (cands["num_matches"], np.float64), "similarity_score": (cands["similarity_score"], np.float64)}
 
 
 def emit(obj):
@@ -323,9 +363,11 @@ def stream_mode(args, pkg, torch, dist, fs, world, rank, local_rank, dev, multi,
     total_dist, total_pairs, total_bytes = (int(x) // args.steps for x in tot.tolist())     # per step, all ranks
     merged, moffs = pkg.sharding.merge_shard_scores(shards, fs.ids, args.gap)
     assert len(merged) == pkg.synth.n_pairs_all_vs_all(n_frames, args.gap) == total_pairs
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, score_fields(merged))
     if rank == 0:
         cpu = None
-        if not multi and args.cpu_seconds > 0:
+        if args.full and not multi and args.cpu_seconds > 0:
             cpu = cpu_baseline_sample(entry, pkg, fs, args.gap, moffs, merged, args.cpu_seconds, args.cpu_threads or host_cores())
         emit(stream_line(args, st, elapsed, total_dist, total_pairs, world, world, n_frames, fs, seed, B, depth, wl_desc, cpu,
                          "process per GPU (torch.distributed)" if multi else "one lcm_handle"))
@@ -574,6 +616,8 @@ def group_mode(args, pkg, torch, entry):
     g.sync()
     t1 = time.perf_counter()
     elapsed = t1 - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, score_fields(sc, ix if argmin_api else None))
     gi = g.info()
     total_dist, total_pairs = int(gi.distances), int(gi.pairs)
     value = total_dist * args.steps / elapsed
@@ -582,10 +626,10 @@ def group_mode(args, pkg, torch, entry):
     slow = int(np.argmax([x.kernel_ms for x in shard_infos]))
     roof, valu = roofline_from_launches(pkg, [shard_infos[slow]], n_desc, argmin_api)
     roof["device"] = slow
-    # parity: byte-identity with the single handle at N = 1 (--force-group), oracle sample otherwise
+    # parity (--full): byte-identity with the single handle at N = 1 (--force-group), oracle sample otherwise
     extra = {}
     cpu = None
-    if W == 1 and not loopback:
+    if args.full and W == 1 and not loopback:
         with pkg.Matcher(p) as m:
             m.set_tuning(pkg.capi.TUNE_PACKED, args.packed)
             m.reserve(n_frames, n_desc)
@@ -607,7 +651,7 @@ def group_mode(args, pkg, torch, entry):
         if args.cpu_seconds > 0:
             cpu = cpu_baseline_sample(entry, pkg, fs, args.gap, offs, sc, args.cpu_seconds, args.cpu_threads or host_cores(),
                                       got_idx=ix if argmin_api else None)
-    else:
+    elif args.full:
         extra["merged_vs_oracle_sample"] = oracle_spot_check(entry, fs, args.gap, offs, sc, ix if argmin_api else None, n_pairs=96)
     out = {
         "metric": METRIC, "value": value, "unit": "distances/s", "n_gpus": 1 if loopback else W, "steps": args.steps,
@@ -635,7 +679,7 @@ def group_mode(args, pkg, torch, entry):
         out["note"] = ("LOOPBACK REHEARSAL: %d shards on ONE GPU, RCCL's transport replaced by device-local copies — the N-device "
                        "code path end to end, NOT a scaling measurement (n_gpus says 1)" % W)
     out.update(extra)
-    if W == 8 and args.workload == "auto" and not args.no_extras and not args.frames:
+    if args.full and W == 8 and args.workload == "auto" and not args.no_extras and not args.frames:
         out["extra"] = {"cfg3_sharded": group_cfg3_extra(pkg, entry, g, args.gap, W, loopback)}
     g.close()
     emit(out)
@@ -713,11 +757,13 @@ def group_stream_mode(args, pkg, entry, g, fs, W, loopback, wl_desc, seed):
     assert len(merged) == total_pairs == int(st.pairs) // args.steps
     total_dist = int(st.distances) // args.steps
     moffs = pkg.sharding.offsets_from_counts(e)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, score_fields(merged))
     cpu = None
     extra = {"note": "PCIe-inclusive online rate (value); the headline metric is the batch mode (inputs resident in HBM)"}
-    if W == 1 and not loopback and args.cpu_seconds > 0:
+    if args.full and W == 1 and not loopback and args.cpu_seconds > 0:
         cpu = cpu_baseline_sample(entry, pkg, fs, args.gap, moffs, merged, args.cpu_seconds, args.cpu_threads or host_cores())
-    else:
+    elif args.full:
         extra["merged_vs_oracle_sample"] = oracle_spot_check(entry, fs, args.gap, moffs, merged, None, n_pairs=240)
     if loopback:
         extra["note"] = ("LOOPBACK REHEARSAL: %d shards on ONE GPU — the N-device streaming path end to end, NOT a scaling "
@@ -751,7 +797,12 @@ def main():
     ap.add_argument("--stream-depth", type=int, default=2, help="--mode stream: micro-batches in flight before the oldest is collected (1..4)")
     ap.add_argument("--online-streams", type=int, default=1, help="--mode stream: 1 = one stream per query slot (default), 0 = the handle's stream only")
     ap.add_argument("--online-split", type=int, default=-1, help="--mode stream: query rows per lane of the split mode (1, 2, 4), 0 = never split, -1 = automatic")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra blocks of the default line (cfg4 fused steps, cfg3 whole, group rehearsals)")
+    ap.add_argument("--full", action="store_true", help="beyond the headline: CPU baseline, oracle samples and single-handle "
+                    "comparisons, per-launch timings, the other row-per-lane kernel, the matrix-core variants and the extra "
+                    "blocks (other configurations) — all outside the timed region; a plain run only times --steps steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the timed path "
+                    "returned in its last step as DIR/<name>.npy (float32 / float64; a fixed seeded sample above 64 MB)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra blocks of the default line (cfg4 fused steps, cfg3 whole, group rehearsals)")
     ap.add_argument("--force-group", action="store_true", help="N = 1 through the product's multi-GPU path (lcm_group_* with one device): "
                     "same value and bytes as the plain line")
     ap.add_argument("--loopback", action="store_true", help="rehearse --gpus N as N shards on ONE device (lcm_group_create_loopback): the "
@@ -906,11 +957,31 @@ def main():
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     elapsed = float(elapsed.item())
 
+    if multi:
+        # merge check (outside the timed region): the gathered shards, un-permuted, must equal what a single device
+        # would have written for a sample of query frames — here verified structurally (lengths, n_train fields)
+        host = recv.view(world, cap).cpu().numpy()
+        shards = [host[r, : lens[r]].view(pkg.capi.SCORE_DTYPE) for r in range(world)]
+        merged, moffs = pkg.sharding.merge_shard_scores(shards, fs.ids, args.gap)
+        exp = pkg.synth.n_pairs_all_vs_all(n_frames, args.gap)
+        assert len(merged) == exp, (len(merged), exp)
+        e = pkg.sharding.eligible_counts(fs.ids, args.gap)
+        nt_expect = np.concatenate([fs.counts[: int(k)] for k in e]) if exp else np.zeros(0)
+        assert np.array_equal(merged["n_train"].astype(np.int64), nt_expect.astype(np.int64)), "merged shard order is wrong"
+    if rank == 0 and args.dump_outputs:
+        if fused:
+            dump_outputs(args.dump_outputs, candidate_fields(fused_out["cands"]))
+        elif multi:
+            dump_outputs(args.dump_outputs, score_fields(merged))
+        else:
+            dump_outputs(args.dump_outputs, score_fields(scores.cpu().numpy().view(pkg.capi.SCORE_DTYPE)[:n_local],
+                                                         idx_sums.cpu().numpy().view(np.uint32)[:n_local] if argmin_api else None))
+
     infos = [m.launch_info()]                                     # HIP events around the LAST timed step's kernels
     loop_test_ms = infos[0].aux_kernel_ms if fused else None
     long_step = infos[0].kernel_ms > 2000.0      # cfg3-sized steps: the timed region's own launches are evidence enough
-    # a few more individually timed steps for stable per-launch durations (outside the timed region)
-    for _ in range(min(3, max(args.steps - 1, 0)) if not (fused or long_step) else 0):
+    # --full: a few more individually timed steps for stable per-launch durations (outside the timed region)
+    for _ in range(min(3, max(args.steps - 1, 0)) if args.full and not (fused or long_step) else 0):
         search((send if multi else scores).data_ptr(), cap if multi else n_local)
         infos.append(m.launch_info())
     info = infos[-1]
@@ -918,9 +989,9 @@ def main():
 
     local_dist = int(info.distances)
     # the same workload through the OTHER row-per-lane kernel, reported beside the headline number: distance-only when the
-    # headline is the argmin kernel, and the other way round
+    # headline is the argmin kernel, and the other way round (--full)
     other_ms = None
-    if args.variant in (0, 1) and not fused and not (multi and long_step):
+    if args.full and args.variant in (0, 1) and not fused and not (multi and long_step):
         ms = []
         for _ in range(1 if long_step else 2):
             if argmin_api:
@@ -933,9 +1004,9 @@ def main():
         m.sync()
 
     # OPT-IN matrix-core variants (north_star rules MFMA out of the product path; these are measurements of what the
-    # rule costs): same workload, same records — compared here — on v_mfma_i32_32x32x32_i8 / the block-scaled fp4 MFMA
+    # rule costs): same workload, same records — compared here — on v_mfma_i32_32x32x32_i8 / the block-scaled fp4 MFMA (--full)
     mfma = None
-    if args.variant in (0, 1) and not fused and not multi and not args.no_extras:
+    if args.full and args.variant in (0, 1) and not fused and not multi and not args.no_extras:
         mfma = {}
         ref = scores.clone()
         ref_idx = idx_sums.clone()
@@ -972,25 +1043,14 @@ def main():
     total_dist, total_pairs, total_bytes = (int(x) for x in tot.tolist())
     value = total_dist * args.steps / elapsed
 
-    # ---- parity spot check + CPU baseline (rank 0, N = 1 only) ---------------------------------------
+    # ---- parity spot check + CPU baseline (--full; rank 0, CPU baseline at N = 1 only) ----------------
     cpu = None
     merged_mismatch = None
-    if multi:
-        # merge check (outside the timed region): the gathered shards, un-permuted, must equal what a single device
-        # would have written for a sample of query frames — here verified structurally (lengths, n_train fields)
-        host = recv.view(world, cap).cpu().numpy()
-        shards = [host[r, : lens[r]].view(pkg.capi.SCORE_DTYPE) for r in range(world)]
-        merged, moffs = pkg.sharding.merge_shard_scores(shards, fs.ids, args.gap)
-        exp = pkg.synth.n_pairs_all_vs_all(n_frames, args.gap)
-        assert len(merged) == exp, (len(merged), exp)
-        e = pkg.sharding.eligible_counts(fs.ids, args.gap)
-        nt_expect = np.concatenate([fs.counts[: int(k)] for k in e]) if exp else np.zeros(0)
-        assert np.array_equal(merged["n_train"].astype(np.int64), nt_expect.astype(np.int64)), "merged shard order is wrong"
-        if rank == 0 and exp:
-            merged_mismatch = oracle_spot_check(entry, fs, args.gap, moffs, merged, None, n_pairs=96)["record_mismatches"]
-    if fused:
+    if args.full and multi and rank == 0 and exp:
+        merged_mismatch = oracle_spot_check(entry, fs, args.gap, moffs, merged, None, n_pairs=96)["record_mismatches"]
+    if args.full and fused:
         fused_scores = m.last_bulk_scores()                  # what the fused call left in HBM (parity sample below)
-    if rank == 0 and not multi and args.cpu_seconds > 0:
+    if args.full and rank == 0 and not multi and args.cpu_seconds > 0:
         torch.cuda.synchronize(dev)
         got = fused_scores if fused else scores.cpu().numpy().view(pkg.capi.SCORE_DTYPE)[:n_local]
         got_idx = idx_sums.cpu().numpy().view(np.uint32)[:n_local] if (argmin_api and not fused) else None
@@ -1046,7 +1106,7 @@ def main():
                             "loop_candidates": int(len(fused_out["cands"])),
                             "note": "roofline covers the score kernels inside the fused call; ms_per_step covers score kernels + "
                                     "loop-test kernels + candidate download"}
-        if not multi and args.workload == "auto" and not args.frames and not args.desc and not args.no_extras:
+        if args.full and not multi and args.workload == "auto" and not args.frames and not args.desc and not args.no_extras:
             single = scores.cpu().numpy().view(pkg.capi.SCORE_DTYPE)[:n_local].copy()
             single_idx = idx_sums.cpu().numpy().view(np.uint32)[:n_local].copy() if argmin_api else None
             m.close()

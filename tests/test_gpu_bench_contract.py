@@ -32,7 +32,7 @@ def last_json(stdout):
 
 def test_single_gpu_contract():
     r = subprocess.run([sys.executable, "bench.py", "--frames", "120", "--desc", "500", "--steps", "2", "--warmup", "1",
-                        "--cpu-seconds", "1"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+                        "--cpu-seconds", "1", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = last_json(r.stdout)
     assert REQUIRED <= set(d)
@@ -48,11 +48,44 @@ def test_single_gpu_contract():
     assert d["value"] > 0 and d["roofline_valu"]["bound"] == "valu"
 
 
+def test_plain_line_is_lean_and_dumps_the_timed_outputs(tmp_path, pkg, oracle):
+    """A plain run times --steps steps and prints the contract's keys without the --full blocks; --dump-outputs writes the
+    last timed step's records and index checksums, the same bytes on every run, equal to the oracle's."""
+    import numpy as np
+    lines = []
+    for k in range(2):
+        r = subprocess.run([sys.executable, "bench.py", "--frames", "120", "--desc", "500", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / str(k))], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(last_json(r.stdout))
+    d = lines[0]
+    assert REQUIRED <= set(d) and d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["cpu_baseline"] is None and d["distance_only_kernel"] is None
+    assert "extra" not in d and "matrix_core_variants" not in d
+    assert d["roofline"]["bound"] == "hbm" and d["roofline_valu"]["bound"] == "valu"
+    names = ("good_count", "min_dist", "n_train", "index_checksum")
+    got = {n: np.load(tmp_path / "0" / (n + ".npy")) for n in names}
+    for n in names:
+        assert got[n].dtype in (np.float32, np.float64)
+        assert np.array_equal(got[n], np.load(tmp_path / "1" / (n + ".npy")))
+    fs = pkg.synth.make_frames(120, 500, seed=pkg.synth.BASE_SEED + 2)
+    pq, pt = [], []
+    for c in range(fs.n_frames):
+        for i in range(fs.n_frames):
+            if fs.ids[c] - fs.ids[i] >= 30:
+                pq.append(c); pt.append(i)
+    assert len(pq) == d["config"]["pairs_per_step"] == len(got["good_count"])
+    want, isum = oracle.fast_score_pairs_idx(fs.rows, fs.counts, pq, pt, oracle.default_params(min_gap=30), n_threads=8)
+    for n in ("good_count", "min_dist", "n_train"):
+        assert np.array_equal(got[n], want[n].astype(got[n].dtype)), n
+    assert np.array_equal(got["index_checksum"], isum.astype(np.float64))
+
+
 def test_two_rank_rehearsal_gloo():
     port = free_port()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--frames", "150",
-                        "--desc", "500", "--steps", "2", "--warmup", "1", "--backend", "gloo", "--cpu-seconds", "0"],
+                        "--desc", "500", "--steps", "2", "--warmup", "1", "--backend", "gloo", "--cpu-seconds", "0", "--full"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = last_json(r.stdout)
@@ -65,7 +98,7 @@ def test_two_rank_rehearsal_gloo():
 def test_stream_mode_contract():
     """--mode stream (configs[4] shape) must carry roofline and cpu_baseline too, and its records must equal the oracle's."""
     r = subprocess.run([sys.executable, "bench.py", "--mode", "stream", "--frames", "150", "--desc", "600", "--steps", "1",
-                        "--warmup", "1", "--cpu-seconds", "1", "--stream-batch", "8"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--cpu-seconds", "1", "--stream-batch", "8", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = last_json(r.stdout)
     assert REQUIRED <= set(d)
@@ -101,7 +134,7 @@ def run_bench(*argv, timeout=900):
 def test_force_group_reproduces_the_plain_line():
     """--gpus 1 --force-group: the N = 1 point of a scaling curve taken through the group path must be the plain
     line's number: same workload, byte-identical records and index checksums, 0 mismatches against the CPU sample."""
-    common = ["--frames", "200", "--desc", "2000", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1", "--no-extras"]
+    common = ["--frames", "200", "--desc", "2000", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1", "--no-extras", "--full"]
     a = run_bench(*common)
     b = run_bench("--gpus", "1", "--force-group", *common)
     assert a.returncode == 0, a.stderr[-2000:]
@@ -129,7 +162,7 @@ def test_n_devices_in_one_process_as_typed_loopback(world):
     """`python3 bench.py --gpus N` with WORLD_SIZE unset takes the in-process route (lcm_group_create(N) ...); on this
     one-GPU box the same command line with --loopback rehearses it (N shards on the one device) — weak-scaled cfg2 shape,
     here with small frames."""
-    r = run_bench("--gpus", str(world), "--loopback", "--desc", "300", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--no-extras")
+    r = run_bench("--gpus", str(world), "--loopback", "--desc", "300", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--no-extras", "--full")
     assert r.returncode == 0, r.stderr[-3000:]
     d = last_json(r.stdout)
     assert REQUIRED <= set(d)
@@ -153,7 +186,7 @@ def test_n_devices_without_enough_gpus_says_so():
 def test_group_stream_mode_loopback():
     """--mode stream --gpus N in one process: asynchronous group tickets (lcm_group_query_submit_batch / _collect_batch)."""
     r = run_bench("--gpus", "3", "--loopback", "--mode", "stream", "--frames", "140", "--desc", "500", "--steps", "1", "--warmup", "1",
-                  "--cpu-seconds", "0", "--stream-batch", "8", "--stream-depth", "3")
+                  "--cpu-seconds", "0", "--stream-batch", "8", "--stream-depth", "3", "--full")
     assert r.returncode == 0, r.stderr[-3000:]
     d = last_json(r.stdout)
     assert REQUIRED <= set(d) and d["n_gpus"] == 1 and d["config"]["batches_in_flight"] == 3

@@ -24,7 +24,7 @@ for k in kernels.values():
     for c in k.values():
         c["per_launch"] = c["sum"] / max(c["dispatches"], 1)
 out = {
-    "command": "rocprofv3 --kernel-trace --pmc <counters> -- python3 bench.py --steps 1 --warmup 0 --cpu-seconds 0 --no-extras "
+    "command": "rocprofv3 --kernel-trace --pmc <counters> -- python3 bench.py --full --steps 1 --warmup 0 --cpu-seconds 0 --no-extras "
                "(separate passes: FETCH_SIZE | WRITE_SIZE | SQ_INSTS_* + GRBM_GUI_ACTIVE | SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAIT_* SQ_WAVE_CYCLES)",
     "units": "FETCH_SIZE / WRITE_SIZE in KB (TCC_EA0 requests x 64 B / 1024), others raw counts; per_launch = sum / dispatches",
     "kernels": kernels,

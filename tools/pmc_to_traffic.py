@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-launch HBM-side traffic of the loop-search kernels from rocprofv3 --pmc passes of
-`bench.py --steps 1 --warmup 0 --cpu-seconds 0 --no-extras` (tools/profile_round.sh) -> profiles/hbm_traffic.json, which
+`bench.py --full --steps 1 --warmup 0 --cpu-seconds 0 --no-extras` (tools/profile_round.sh) -> profiles/hbm_traffic.json, which
 bench.py reports as roofline.traffic (per SCORE LAUNCH, like roofline.achieved).
 
 READS come from the size-resolved request counters of the L2's memory-side interface, which exist on gfx950:

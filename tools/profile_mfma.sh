@@ -5,7 +5,7 @@ TAG=${1:-r02}
 OUT=$PWD/gpurun_out/${TAG}_mfma${VAR:-4}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-B="python3 $PWD/bench.py"
+B="python3 $PWD/bench.py --full"
 rocprofv3 --kernel-trace --stats -d "$OUT/kt" -o kt --output-format csv -- $B --variant ${VAR:-4} --cpu-seconds 0 --no-extras > "$OUT/kt_bench.json" 2> "$OUT/kt.log"
 echo "kt rc=$?"
 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU GRBM_GUI_ACTIVE -d "$OUT/sq" -o p --output-format csv -- $B --variant ${VAR:-4} --steps 1 --warmup 0 --cpu-seconds 0 --no-extras > /dev/null 2> "$OUT/sq.log"

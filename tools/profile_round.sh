@@ -10,7 +10,7 @@ QUICK=${2:-}
 OUT=$PWD/gpurun_out/${TAG}_prof
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-B="python3 $PWD/bench.py"
+B="python3 $PWD/bench.py --full"
 ONE="--steps 1 --warmup 0 --cpu-seconds 0 --no-extras"
 cd "$PWD"
 # 1. per-kernel time of the default bench command (no CPU leg, no extras: the kernels of the timed region only)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The online (streaming) path through its three forms, one table (profiles/r03_stream_group.txt):
     python tools/stream_table.py [--frames 2500,5000,20000] [--forms single,group1,group8] > profiles/rNN_stream_group.txt
-Each cell is one `bench.py --mode stream --frames F --steps 1 --warmup 0` in its own process (a pass from an EMPTY
+Each cell is one `bench.py --mode stream --frames F --steps 1 --warmup 0 --full` in its own process (a pass from an EMPTY
 database, micro-batches of 8, 2 in flight, host rows over PCIe, wall clock):
     single  = one lcm_handle                      (lcm_query_submit_batch / _collect_batch)
     group1  = --gpus 1 --force-group              (lcm_group_query_submit_batch / _collect_batch, RCCL communicator of one)
@@ -31,7 +31,7 @@ def main():
             if form == "group1" and frames >= 20000:
                 continue                                  # same code path as group8 minus the threads: not worth 3 more minutes
             cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "stream", "--frames", str(frames), "--steps", "1",
-                   "--warmup", "0", "--cpu-seconds", "2"] + FORMS[form]
+                   "--warmup", "0", "--cpu-seconds", "2", "--full"] + FORMS[form]
             r = subprocess.run(cmd, capture_output=True, text=True)
             if r.returncode != 0:
                 print(f"{frames:6d}  {form:7s}  FAILED rc={r.returncode}: {r.stderr.strip().splitlines()[-1] if r.stderr.strip() else ''}")

@@ -3,7 +3,7 @@
 
 Inputs: two rocprofv3 --pmc passes collected by tools/profile_round.sh with the same counter set
 (SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY
-GRBM_GUI_ACTIVE): <prof>/valu (bench.py --steps 1 --warmup 0 --cpu-seconds 0 --no-extras) and <prof>/valu_ref
+GRBM_GUI_ACTIVE): <prof>/valu (bench.py --full --steps 1 --warmup 0 --cpu-seconds 0 --no-extras) and <prof>/valu_ref
 (tools/valu_busy: a pure v_xor_b32 loop, a pure v_bcnt_u32_b32 loop, the inner-loop mix without memory traffic).
 
 What the counters say on gfx950 (checked against the reference loops' known instruction counts): SQ_ACTIVE_INST_VALU
@@ -56,7 +56,7 @@ for name, c in ref.items():
             refs[key] = derived(c)
 cost_xor = refs["k_pure_xor"]["simd_cycles_per_valu_instruction"]
 cost_bcnt = refs["k_pure_bcnt"]["simd_cycles_per_valu_instruction"]
-out = {"source": "rocprofv3 --pmc passes of bench.py --steps 1 --warmup 0 --cpu-seconds 0 --no-extras and of tools/valu_busy "
+out = {"source": "rocprofv3 --pmc passes of bench.py --full --steps 1 --warmup 0 --cpu-seconds 0 --no-extras and of tools/valu_busy "
                  "(tools/profile_round.sh), summarised by tools/valu_busy_summary.py",
        "reference_loops": refs,
        "issue_cost_simd_cycles": {"v_xor_b32 (pure loop)": cost_xor, "v_bcnt_u32_b32 (pure loop)": cost_bcnt,
