@@ -86,7 +86,10 @@ int grow_arena(lcm_handle* h, int need_frames, int need_rows) {
     int new_cap = h->cap_frames;
     if (need_frames > new_cap) new_cap = std::max(need_frames, std::max(64, h->cap_frames * 2));
     if (new_stride == h->stride_rows && new_cap == h->cap_frames && h->d_rows) return LCM_OK;
-    if (new_stride > 65535) return fail(LCM_ERR_CAPACITY, "a stored frame may hold at most 65535 rows (got %d)", need_rows);
+    // need_rows is the caller's row count or the stride the arena already has: the limit is on the ROWS of a frame
+    // (MAX_FRAME_ROWS), the stride is that rounded up to ROW_PAD and so reaches 65536
+    if (new_stride > round_up(MAX_FRAME_ROWS, ROW_PAD))
+        return fail(LCM_ERR_CAPACITY, "a stored frame may hold at most %d rows (got %d)", MAX_FRAME_ROWS, need_rows);
 
     uint8_t* nrows = nullptr;
     int32_t* ncounts = nullptr;
@@ -133,6 +136,7 @@ int grow_arena(lcm_handle* h, int need_frames, int need_rows) {
 
 int check_append(lcm_handle* h, int frame_id, int n) {
     if (n < 0) return fail(LCM_ERR_INVALID_ARG, "negative row count %d", n);
+    if (n > MAX_FRAME_ROWS) return fail(LCM_ERR_CAPACITY, "a stored frame may hold at most %d rows (got %d)", MAX_FRAME_ROWS, n);
     if (!h->frames.empty() && frame_id <= h->frames.back().id)
         return fail(LCM_ERR_ORDER, "frame id %d appended after id %d: ids must be strictly increasing", frame_id,
                     h->frames.back().id);
@@ -315,6 +319,7 @@ int lcm_set_tuning(lcm_handle* h, int knob, int value) {
 
 static int db_reserve_impl(lcm_handle* h, int n_frames, int max_desc) {
     if (!h || n_frames < 0 || max_desc < 0) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+    if (max_desc > MAX_FRAME_ROWS) return fail(LCM_ERR_CAPACITY, "a stored frame may hold at most %d rows (got %d)", MAX_FRAME_ROWS, max_desc);
     int rc = set_device(h); if (rc) return rc;
     return grow_arena(h, std::max(n_frames, 1), std::max(max_desc, 1));
 }

@@ -574,7 +574,8 @@ int group_search(lcm_group* g, SearchMode mode, lcm_score* out_scores, uint32_t*
     for (lcm_handle* h : g->h) stride = std::max(stride, h->stride_rows);
     for (const GFrame& f : g->frames) stride = std::max(stride, (f.n + 3) / 4 * 4);
     for (int r = 0; r < W; ++r) {
-        int rc = lcm_db_reserve(g->h[(size_t)r], shard_cap, stride); if (rc) return rc;
+        // `stride` is a padded row count (up to 65536); lcm_db_reserve takes the rows of a frame (up to 65535) and pads them itself
+        int rc = lcm_db_reserve(g->h[(size_t)r], shard_cap, std::min(stride, MAX_FRAME_ROWS)); if (rc) return rc;
         if (g->h[(size_t)r]->stride_rows != stride || g->h[(size_t)r]->cap_frames < shard_cap)
             return fail(LCM_ERR_HIP, "shard %d arena geometry mismatch", r);
     }

@@ -50,6 +50,7 @@ int guarded(F&& f) noexcept {
     } while (0)
 
 constexpr int ROW_PAD = 4;            // stored rows are padded to a multiple of 4 with copies of the last row
+constexpr int MAX_FRAME_ROWS = 65535; // include/lcm.h: rows of one frame (the record's n_train is 16 bits); the arena stride reaches 65536
 constexpr size_t ARENA_SLACK = 512;   // the kernel prefetches up to 4 rows past a frame's padded end
 constexpr int DEFAULT_MAX_DESC = 2000;  // ORB nfeatures of the reference (README.md:114)
 
