@@ -11,6 +11,8 @@
  *   lcm_match_features    <- LoopClosingSystem::matchFeatures incl. the "2 x minimum distance"
  *                            filter (include/loop_closing.hpp:40, README.md:116-117)
  *   lcm_match_stored      <- matchFeatures on two frames of frames_ (README.md:101 re-match of loop frames)
+ *   lcm_match_features_ratio <- matchFeatures(desc1, desc2, good, ratio): knnMatch(k = 2) + Lowe's ratio test
+ *                            (src/main.cpp:509-534), and its stored-frame / batch forms
  *   lcm_db_append*        <- `frames_.push_back(frame)` inside processFrame
  *                            (include/loop_closing.hpp:34,69) — the stored-frame descriptor database
  *   lcm_query_scores      <- the per-stored-frame loop inside detectLoops
@@ -217,6 +219,34 @@ LCM_API int  lcm_match_stored_batch(lcm_handle* h, const lcm_pair_ref* pairs, in
 /* ... and one query frame given by the host (the current frame, not stored yet) against n_trains stored frames. */
 LCM_API int  lcm_match_query_batch(lcm_handle* h, const uint8_t* query, int nq, const int32_t* train_frame_ids, int n_trains,
                                    lcm_dmatch* out, size_t cap, size_t* offsets, int32_t* min_dists);
+
+/* ---- pair mode, two neighbours: BFMatcher(NORM_HAMMING, crossCheck=false).knnMatch(k = 2) + Lowe's ratio test ---- */
+/* The matcher the reference actually runs (src/main.cpp:509-534): for each query row the two nearest train rows in
+ * OpenCV's batchDistance order — ascending by distance, the lower train index first among equal distances, i.e. the two
+ * smallest (distance, train index) pairs — then `best` is kept iff best.distance < ratio * second.distance (strict,
+ * evaluated in IEEE double) and a query row with fewer than two neighbours is dropped.  It is used with ratio 0.75 for
+ * consecutive frames (src/main.cpp:1154) and 0.7 for the loop search (:1386).  These calls do not consult
+ * lcm_params.ratio / dist_floor; they return LCM_ERR_INVALID_ARG while cross_check != 0 (OpenCV asserts knn == 1 under
+ * crossCheck) and for a ratio that is NaN or negative.  Errors, capacities, empty sides and `offsets` are those of the
+ * k = 1 calls above; records have img_idx = 0 and the integer-valued distance of `best`. */
+/* knnMatch(k=2) (src/main.cpp:520): train_idx[2*q + k], dist[2*q + k], k = 0 best, 1 second; a missing second neighbour
+ * (nt == 1) is train_idx = -1, dist = 0xFFFF.  *n_neighbours = min(nt, 2), 0 if either side is empty (nothing written then). */
+LCM_API int  lcm_knn2_pair(lcm_handle* h, const uint8_t* query, int nq, const uint8_t* train, int nt,
+                           int32_t* train_idx, uint16_t* dist, int* n_neighbours);
+/* matchFeatures(desc1, desc2, good, ratio) (src/main.cpp:509-534): the above + the ratio test, query order preserved.
+ * `out` needs room for nq records. */
+LCM_API int  lcm_match_features_ratio(lcm_handle* h, const uint8_t* query, int nq, const uint8_t* train, int nt, double ratio,
+                                      lcm_dmatch* out, int* n_out);
+/* The same between two STORED frames (src/main.cpp:1386 matches keyframe descriptors that are already kept). */
+LCM_API int  lcm_match_stored_ratio(lcm_handle* h, int query_frame_id, int train_frame_id, double ratio,
+                                    lcm_dmatch* out, int cap, int* n_out);
+/* ... for MANY stored pairs in ONE launch: the reference's loop search (src/main.cpp:1375-1388 counts the ratio-test
+ * survivors of the current keyframe against every earlier one).  The match count of pair p is offsets[p+1] - offsets[p]. */
+LCM_API int  lcm_match_stored_batch_ratio(lcm_handle* h, const lcm_pair_ref* pairs, int n_pairs, double ratio,
+                                          lcm_dmatch* out, size_t cap, size_t* offsets);
+/* ... and one query frame given by the host (the current frame, src/main.cpp:1386's desc1) against n_trains stored frames. */
+LCM_API int  lcm_match_query_batch_ratio(lcm_handle* h, const uint8_t* query, int nq, const int32_t* train_frame_ids, int n_trains,
+                                         double ratio, lcm_dmatch* out, size_t cap, size_t* offsets);
 
 /* ---- loop search against the stored database --------------------------------------------------------- */
 /* Score `query` (id query_frame_id) against every stored frame with query_frame_id - id >= min_gap, ascending

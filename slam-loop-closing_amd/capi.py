@@ -112,6 +112,11 @@ _SIGNATURES = {
     "lcm_match_stored": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _i32p, _i32p]),
     "lcm_match_stored_batch": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_size_t, _vp, _vp]),
     "lcm_match_query_batch": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_size_t, _vp, _vp]),
+    "lcm_knn2_pair": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _i32p]),
+    "lcm_match_features_ratio": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_double, _vp, _i32p]),
+    "lcm_match_stored_ratio": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, _vp, C.c_int, _i32p]),
+    "lcm_match_stored_batch_ratio": (C.c_int, [_vp, _vp, C.c_int, C.c_double, _vp, C.c_size_t, _vp]),
+    "lcm_match_query_batch_ratio": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_double, _vp, C.c_size_t, _vp]),
     "lcm_query_scores": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _i32p]),
     "lcm_query_submit": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _i32p]),
     "lcm_query_collect": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i32p]),
@@ -353,6 +358,60 @@ class Matcher:
         _check(self._lib.lcm_match_query_batch(self._h, _ptr(q), q.shape[0], _ptr(ids), n, out.ctypes.data_as(_vp), cap,
                                                offs.ctypes.data_as(_vp), md.ctypes.data_as(_vp)))
         return [out[int(offs[i]): int(offs[i + 1])] for i in range(n)], md[:n]
+
+    # -- pair mode, two neighbours + Lowe's ratio test ----------------------------------------------
+    def knn2_pair(self, query, train) -> Tuple[np.ndarray, np.ndarray]:
+        """BFMatcher(NORM_HAMMING).knnMatch(k=2): (train_idx int32[nq, 2], dist uint16[nq, 2]), best first; a missing
+        second neighbour (one train row) is (-1, 0xFFFF); nq = 0 rows if either side is empty."""
+        q, t = _rows(query), _rows(train)
+        idx = np.empty((q.shape[0], 2), np.int32)
+        dist = np.empty((q.shape[0], 2), np.uint16)
+        n = C.c_int32(0)
+        _check(self._lib.lcm_knn2_pair(self._h, _ptr(q), q.shape[0], _ptr(t), t.shape[0], _ptr(idx), _ptr(dist),
+                                       C.byref(n)))
+        rows = q.shape[0] if n.value else 0
+        return idx[:rows], dist[:rows]
+
+    def match_features_ratio(self, query, train, ratio: float) -> np.ndarray:
+        """matchFeatures(desc1, desc2, good, ratio): knnMatch(k=2) + Lowe's ratio test -> DMatch records, query order."""
+        q, t = _rows(query), _rows(train)
+        out = np.zeros(max(q.shape[0], 1), DMATCH_DTYPE)
+        n = C.c_int32(0)
+        _check(self._lib.lcm_match_features_ratio(self._h, _ptr(q), q.shape[0], _ptr(t), t.shape[0], ratio,
+                                                  out.ctypes.data_as(_vp), C.byref(n)))
+        return out[: n.value]
+
+    def match_stored_ratio(self, query_frame_id: int, train_frame_id: int, ratio: float, cap: int = 65536) -> np.ndarray:
+        """The same between two stored frames (device-resident rows)."""
+        out = np.zeros(max(cap, 1), DMATCH_DTYPE)
+        n = C.c_int32(0)
+        _check(self._lib.lcm_match_stored_ratio(self._h, query_frame_id, train_frame_id, ratio, out.ctypes.data_as(_vp), cap,
+                                                C.byref(n)))
+        return out[: n.value]
+
+    def match_stored_batch_ratio(self, pairs: Sequence[Tuple[int, int]], ratio: float, cap: Optional[int] = None):
+        """Ratio-filtered match lists of many stored (query id, train id) pairs in one launch: (list of DMatch arrays,
+        offsets[n + 1])."""
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n = pr.shape[0]
+        cap = 2048 * max(n, 1) if cap is None else cap
+        out = np.zeros(max(cap, 1), DMATCH_DTYPE)
+        offs = np.zeros(n + 1, np.uintp)
+        _check(self._lib.lcm_match_stored_batch_ratio(self._h, _ptr(pr), n, ratio, out.ctypes.data_as(_vp), cap,
+                                                      offs.ctypes.data_as(_vp)))
+        return [out[int(offs[i]): int(offs[i + 1])] for i in range(n)], offs
+
+    def match_query_batch_ratio(self, query, train_ids: Sequence[int], ratio: float, cap: Optional[int] = None):
+        """One host query frame against many stored frames in one launch: (list of DMatch arrays, offsets[n + 1])."""
+        q = _rows(query)
+        ids = np.ascontiguousarray(train_ids, np.int32)
+        n = ids.shape[0]
+        cap = max(q.shape[0], 1) * max(n, 1) if cap is None else cap
+        out = np.zeros(max(cap, 1), DMATCH_DTYPE)
+        offs = np.zeros(n + 1, np.uintp)
+        _check(self._lib.lcm_match_query_batch_ratio(self._h, _ptr(q), q.shape[0], _ptr(ids), n, ratio,
+                                                     out.ctypes.data_as(_vp), cap, offs.ctypes.data_as(_vp)))
+        return [out[int(offs[i]): int(offs[i + 1])] for i in range(n)], offs
 
     # -- loop search -------------------------------------------------------------------------------
     def query_scores(self, query, query_frame_id: int) -> Tuple[np.ndarray, np.ndarray]:

@@ -3,6 +3,7 @@
 //   lcm_pair.cpp       pair mode / match lists        lcm_online.cpp   online queries (single, micro-batch), detectLoops
 //   lcm_bulk.cpp       bulk all-vs-all, fused loops   lcm_cross.cpp    cross_check scoring
 //   lcm_mfma_host.cpp  opt-in matrix-core variants    lcm_group.cpp    multi-GPU group (RCCL)
+//   lcm_knn.cpp        pair mode with k = 2 neighbours + Lowe's ratio test
 // Not installed; the public surface is include/lcm.h.
 #pragma once
 #include "../../include/lcm.h"
@@ -276,12 +277,34 @@ int all_vs_all(lcm_handle* h, const void* d_query_rows, const int32_t* d_query_c
 int loop_test_device(lcm_handle* h, const void* d_scores, size_t n_pairs, const uint32_t* offsets, int n_q,
                      const int32_t* q_ids, const int32_t* q_kp, int n_db, const int32_t* db_ids, const int32_t* db_kp,
                      size_t cap, size_t* n_found);
+// ---- lcm_pair.cpp: the pair mode's plumbing, shared with lcm_knn.cpp.  k = neighbours per query row: 1 (match) or 2
+// (knnMatch(k = 2)); with k = 2 every key array holds 2 keys per query row (best, second; 0xFFFFFFFF = none).
+// Row source: host rows (uploaded to scratch) or rows already on the device (a stored frame).
+struct RowSrc {
+    const uint8_t* host;
+    const uint8_t* dev;
+    int n;
+};
+// One matchFeatures job of a batch: query rows x train rows, both given as ROW INDICES into one query matrix and one
+// train matrix on the device (the database arena, or this call's staging block).
+struct PairJob { uint32_t q_row; int nq; uint32_t t_row; int nt; };
+int run_pair_jobs(lcm_handle* h, const uint8_t* d_q_base, const uint8_t* d_t_base, bool q_in_stage, bool t_in_stage,
+                  size_t stage_bytes, const std::vector<PairJob>& jobs, const uint32_t** keys_out, std::vector<size_t>& row0,
+                  int k = 1);
+int pair_keys(lcm_handle* h, RowSrc q, RowSrc t, std::vector<uint32_t>& keys_out, int cross, int k = 1);
+int stored_src(lcm_handle* h, int frame_id, RowSrc* out, int* n_kp);    // device rows + row counts of a stored frame
+// The jobs of a batch call (q_host != NULL: one host query frame, staged at the head of h_pair_stage, against the stored
+// frames train_ids; else the stored pairs): job_of[p] = pair p's job, -1 when a side is empty.
+int batch_jobs(lcm_handle* h, const uint8_t* q_host, int nq_host, const lcm_pair_ref* pairs, const int32_t* train_ids,
+               int n_pairs, std::vector<PairJob>& jobs, std::vector<int>& job_of, size_t* stage_bytes);
 }  // namespace lcm
 
 namespace {
 using lcm::cross_score_prefixes;
 using lcm::eligible_prefix;
 using lcm::launch_and_time;
+using lcm::PairJob;
+using lcm::RowSrc;
 using lcm::mfma_bulk;
 using lcm::mfma_online;
 using lcm::pick_chunk;

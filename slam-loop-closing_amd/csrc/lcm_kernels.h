@@ -134,6 +134,25 @@ hipError_t launch_upload(void* d_dst, const void* h_src_pinned, size_t bytes, hi
 // (2000 x 2000: 252 workgroups x 4 waves x 64 distances per lane instead of 63 x 4 x 256).
 hipError_t launch_score_pairs_small(const ScoreArgs& a, uint32_t n_items, hipStream_t st);
 
+// ---- pair mode, k = 2 (lcm_knn.hip): knnMatch(k = 2) of src/main.cpp:509-534 ------------------------------------------
+// The same PairItem work items; per (item, query row) the TWO smallest packed keys (segment-local train indices) go to
+// keys[(out_offset * keys_stride + row) * 2 + {0, 1}], 0xFFFFFFFF = no such neighbour (a segment of one row has no
+// second).  The padding rows past an item's nt rows never become neighbours.  keys must be 8-byte aligned.
+struct Knn2Args {
+    const uint32_t* q_rows;      // query rows: item's rows start at row q_row (rows of 8 dwords)
+    const uint32_t* t_rows;      // train rows, same layout
+    const PairItem* items;
+    uint32_t*       keys;
+    uint32_t        keys_stride; // query rows per item: 2048 (throughput shape) or 512 (latency shape)
+};
+// Throughput shape: items of <= 2048 query rows, 8 rows per lane (workgroup size by max_query_rows, as launch_score).
+hipError_t launch_knn2_pairs(const Knn2Args& a, uint32_t n_items, int max_query_rows, hipStream_t st);
+// Latency shape: items of <= 512 query rows on 256-thread workgroups of 2 rows per lane (see launch_score_pairs_small).
+hipError_t launch_knn2_pairs_small(const Knn2Args& a, uint32_t n_items, hipStream_t st);
+// The twin of launch_fold_pair_keys: merges the per-segment top-2 lists into every query row's two smallest keys with
+// GLOBAL train indices, final_keys[(out_row0 + r) * 2 + {0, 1}] (seg_keys: chunk_rows key PAIRS per item).
+hipError_t launch_fold_pair_keys2(const FoldArgs& a, uint32_t max_nq, hipStream_t st);
+
 // On-device loop test over a finished score array (BASELINE.json configs[3] "fused on-device filter + loop test"):
 // pair p belongs to query frame c = upper_bound(offsets, p) - 1 and stored slot p - offsets[c]; a candidate is
 // similarity = good / min(kp_q, kp_t) > sim_threshold (IEEE double, strict) and good >= min_matches.  Candidates

@@ -2,20 +2,9 @@
 // Part of liblcm_hip.so's host side (C ABI in include/lcm.h); shared state and helpers: lcm_internal.h.
 #include "lcm_internal.h"
 
-extern "C" {
-
 /* ---- pair mode --------------------------------------------------------------------------------------- */
 
-// Row source of the pair mode: host rows (uploaded to scratch) or rows already on the device (a stored frame).
-struct RowSrc {
-    const uint8_t* host;
-    const uint8_t* dev;
-    int n;
-};
-
-// One matchFeatures job of a batch: query rows x train rows, both given as ROW INDICES into one query matrix and one
-// train matrix on the device (the database arena, or this call's staging block).
-struct PairJob { uint32_t q_row; int nq; uint32_t t_row; int nt; };
+namespace lcm {
 
 // Best packed key (dist << 22 | GLOBAL train index) of every query row of every job -> keys (pinned host memory owned
 // by the handle; job p's rows start at row0[p]).
@@ -26,8 +15,9 @@ struct PairJob { uint32_t q_row; int nq; uint32_t t_row; int nt; };
 // segment-local train indices; the fold adds the segment base and takes the min, so the FIRST minimum wins across
 // segments), ONE download.  `stage_bytes` bytes at h->h_pair_stage (already filled by the caller with any host rows)
 // precede the items / descriptors this function appends, and the whole block goes up in ONE hipMemcpyAsync.
-static int run_pair_jobs(lcm_handle* h, const uint8_t* d_q_base, const uint8_t* d_t_base, bool q_in_stage, bool t_in_stage,
-                         size_t stage_bytes, const std::vector<PairJob>& jobs, const uint32_t** keys_out, std::vector<size_t>& row0) {
+// k = 2 (lcm_knn.cpp): the same plan through the two-neighbour kernels; keys holds 2 keys per query row.
+int run_pair_jobs(lcm_handle* h, const uint8_t* d_q_base, const uint8_t* d_t_base, bool q_in_stage, bool t_in_stage,
+                  size_t stage_bytes, const std::vector<PairJob>& jobs, const uint32_t** keys_out, std::vector<size_t>& row0, int k) {
     const size_t P = jobs.size();
     // Work-item shape.  Throughput shape: query chunks of 2048 rows (8 per lane).  LATENCY shape, for calls of up to 64 M
     // distances (one matchFeatures of 2000 x 2000 is 4 M): chunks of 512 rows (2 per lane) — four times the waves with a
@@ -83,8 +73,8 @@ static int run_pair_jobs(lcm_handle* h, const uint8_t* d_q_base, const uint8_t* 
     rc = ensure_dev(h->d_pair_stage, h->d_pair_stage_bytes, up_bytes, ARENA_SLACK); if (rc) return rc;
     memcpy(h->h_pair_stage + off_items, items.data(), sizeof(lcm::PairItem) * n_items);
     memcpy(h->h_pair_stage + off_descs, descs.data(), sizeof(lcm::PairDesc) * P);
-    rc = ensure_dev(h->d_keys, h->d_keys_n, n_items * (size_t)CH + total_rows); if (rc) return rc;
-    rc = ensure_pinned(h->h_final_keys, h->h_final_keys_n, total_rows); if (rc) return rc;
+    rc = ensure_dev(h->d_keys, h->d_keys_n, (n_items * (size_t)CH + total_rows) * (size_t)k); if (rc) return rc;
+    rc = ensure_pinned(h->h_final_keys, h->h_final_keys_n, total_rows * (size_t)k); if (rc) return rc;
     // only the part the caller did not fill needs the copy when the rows are device-resident already
     const size_t up_from = (q_in_stage || t_in_stage) ? 0 : off_items;
     if (small && h->tune_pair_upload_kernel) {
@@ -103,9 +93,16 @@ static int run_pair_jobs(lcm_handle* h, const uint8_t* d_q_base, const uint8_t* 
     a.pair_items = reinterpret_cast<const lcm::PairItem*>(h->d_pair_stage + off_items);
     a.scores = nullptr; a.keys = h->d_keys; a.keys_stride = CH;
     a.ratio = h->params.ratio; a.dist_floor = h->params.dist_floor;
-    if (small) {
+    if (small || k == 2) {
         HIP_TRY(hipEventRecord(h->ev_start, h->stream));
-        const hipError_t e1 = lcm::launch_score_pairs_small(a, (uint32_t)n_items, h->stream);
+        hipError_t e1;
+        if (k == 2) {
+            const lcm::Knn2Args ka{a.q_rows, a.db_rows, a.pair_items, h->d_keys, (uint32_t)CH};
+            e1 = small ? lcm::launch_knn2_pairs_small(ka, (uint32_t)n_items, h->stream)
+                       : lcm::launch_knn2_pairs(ka, (uint32_t)n_items, std::min(max_nq, CH), h->stream);
+        } else {
+            e1 = lcm::launch_score_pairs_small(a, (uint32_t)n_items, h->stream);
+        }
         if (e1 != hipSuccess) return fail(LCM_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e1));
         HIP_TRY(hipEventRecord(h->ev_stop, h->stream));
         h->info_pending = true;
@@ -121,9 +118,9 @@ static int run_pair_jobs(lcm_handle* h, const uint8_t* d_q_base, const uint8_t* 
     // address space; 4 bytes per query row over PCIe), so no device-to-host copy packet follows it: the stream's
     // synchronisation below is also the hand-over.  Throughput shape: device buffer + one copy.
     const bool host_fold = small && h->tune_pair_host_fold;
-    f.final_keys = host_fold ? h->h_final_keys : h->d_keys + n_items * (size_t)CH;
+    f.final_keys = host_fold ? h->h_final_keys : h->d_keys + n_items * (size_t)CH * (size_t)k;
     f.n_pairs = (uint32_t)P;
-    hipError_t e = lcm::launch_fold_pair_keys(f, (uint32_t)max_nq, h->stream);
+    hipError_t e = k == 2 ? lcm::launch_fold_pair_keys2(f, (uint32_t)max_nq, h->stream) : lcm::launch_fold_pair_keys(f, (uint32_t)max_nq, h->stream);
     if (e != hipSuccess) return fail(LCM_ERR_HIP, "fold kernel launch failed: %s", hipGetErrorString(e));
     h->info.launches = 2;
     h->info.pairs = P; h->info.distances = 0; h->info.algo_bytes = 0;
@@ -131,7 +128,7 @@ static int run_pair_jobs(lcm_handle* h, const uint8_t* d_q_base, const uint8_t* 
         h->info.distances += (uint64_t)jb.nq * (uint64_t)jb.nt;
         h->info.algo_bytes += (uint64_t)jb.nt * 32 + (uint64_t)jb.nq * 32 + 8;
     }
-    if (!host_fold) HIP_TRY(hipMemcpyAsync(h->h_final_keys, f.final_keys, sizeof(uint32_t) * total_rows, hipMemcpyDeviceToHost, h->stream));
+    if (!host_fold) HIP_TRY(hipMemcpyAsync(h->h_final_keys, f.final_keys, sizeof(uint32_t) * total_rows * (size_t)k, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     *keys_out = h->h_final_keys;
     return LCM_OK;
@@ -160,7 +157,7 @@ static void cross_combine(int mode, const uint32_t* fkeys, int nq, const uint32_
 // `cross` = the cross-check mode to apply (the handle's, for the outer call; 0 for the two one-directional passes the
 // cross-check itself is made of).  It is an ARGUMENT: the handle's parameters are never touched, so no failure in the
 // nested passes — an exception included — can leave the handle with its cross-check switched off.
-static int pair_keys(lcm_handle* h, RowSrc q, RowSrc t, std::vector<uint32_t>& keys_out, int cross) {
+int pair_keys(lcm_handle* h, RowSrc q, RowSrc t, std::vector<uint32_t>& keys_out, int cross, int k) {
     int rc = set_device(h); if (rc) return rc;
     if (cross) {
         if (q.n > LCM_MAX_TRAIN_ROWS) return fail(LCM_ERR_CAPACITY, "cross_check: at most %d query rows", LCM_MAX_TRAIN_ROWS);
@@ -195,13 +192,13 @@ static int pair_keys(lcm_handle* h, RowSrc q, RowSrc t, std::vector<uint32_t>& k
     jobs[0].t_row = t.dev ? (uint32_t)((size_t)(t.dev - h->d_rows) / LCM_DESC_BYTES) : (uint32_t)(t_off / LCM_DESC_BYTES);
     const uint32_t* keys = nullptr;
     std::vector<size_t> row0;
-    rc = run_pair_jobs(h, h->d_rows, h->d_rows, !q.dev, !t.dev, stage_bytes, jobs, &keys, row0); if (rc) return rc;
-    keys_out.assign(keys, keys + q.n);
+    rc = run_pair_jobs(h, h->d_rows, h->d_rows, !q.dev, !t.dev, stage_bytes, jobs, &keys, row0, k); if (rc) return rc;
+    keys_out.assign(keys, keys + (size_t)q.n * (size_t)k);
     return LCM_OK;
 }
 
 // Device rows + row counts of a stored frame.
-static int stored_src(lcm_handle* h, int frame_id, RowSrc* out, int* n_kp) {
+int stored_src(lcm_handle* h, int frame_id, RowSrc* out, int* n_kp) {
     int lo = 0, hi = (int)h->frames.size();
     while (lo < hi) { int mid = (lo + hi) / 2; if (h->frames[mid].id < frame_id) lo = mid + 1; else hi = mid; }
     if (lo >= (int)h->frames.size() || h->frames[lo].id != frame_id) return fail(LCM_ERR_NOT_FOUND, "frame id %d is not stored", frame_id);
@@ -211,6 +208,45 @@ static int stored_src(lcm_handle* h, int frame_id, RowSrc* out, int* n_kp) {
     if (n_kp) *n_kp = h->frames[lo].n_kp;
     return LCM_OK;
 }
+
+int batch_jobs(lcm_handle* h, const uint8_t* q_host, int nq_host, const lcm_pair_ref* pairs, const int32_t* train_ids,
+               int n_pairs, std::vector<PairJob>& jobs, std::vector<int>& job_of, size_t* stage_bytes) {
+    int rc = LCM_OK;
+    jobs.clear();
+    job_of.assign((size_t)n_pairs, -1);
+    *stage_bytes = 0;
+    if (q_host && nq_host > 0) {
+        *stage_bytes = (size_t)nq_host * LCM_DESC_BYTES;
+        rc = ensure_pinned(h->h_pair_stage, h->h_pair_stage_bytes, *stage_bytes + 65536 + (size_t)n_pairs * 2048); if (rc) return rc;
+        memcpy(h->h_pair_stage, q_host, *stage_bytes);
+    }
+    for (int p = 0; p < n_pairs; ++p) {
+        RowSrc q{}, t{};
+        if (q_host) { q.host = q_host; q.n = nq_host; }
+        else { rc = stored_src(h, pairs[p].query_frame_id, &q, nullptr); if (rc) return rc; }
+        rc = stored_src(h, q_host ? train_ids[p] : pairs[p].train_frame_id, &t, nullptr); if (rc) return rc;
+        if (q.n == 0 || t.n == 0) continue;                     // BFMatcher: an empty side => no matches
+        job_of[(size_t)p] = (int)jobs.size();
+        jobs.push_back({q.dev ? (uint32_t)((size_t)(q.dev - h->d_rows) / LCM_DESC_BYTES) : 0u, q.n,
+                        (uint32_t)((size_t)(t.dev - h->d_rows) / LCM_DESC_BYTES), t.n});
+    }
+    rc = wait_db(h); if (rc) return rc;
+    if ((size_t)h->cap_frames * (size_t)h->stride_rows >= 0xFFFFFFFFull)
+        return fail(LCM_ERR_CAPACITY, "the database arena exceeds 2^32 rows: pair items address rows with 32 bits");
+    return LCM_OK;
+}
+
+}  // namespace lcm
+
+namespace {
+using lcm::batch_jobs;
+using lcm::cross_combine;
+using lcm::pair_keys;
+using lcm::run_pair_jobs;
+using lcm::stored_src;
+}  // namespace
+
+extern "C" {
 
 static int filter_keys(const lcm_handle* h, const std::vector<uint32_t>& keys, int nq, lcm_dmatch* out, int* n_out, int* min_dist) {
     // README.md:117 filter on the shipped integers (O(nq) bookkeeping)
@@ -310,26 +346,9 @@ static int match_batch_impl(lcm_handle* h, const uint8_t* q_host, int nq_host, c
     int rc = set_device(h); if (rc) return rc;
     if (q_host && nq_host > lcm::MAX_FUSED_QUERY_ROWS * 64) return fail(LCM_ERR_CAPACITY, "query frame too large");
     std::vector<PairJob> jobs;
-    std::vector<int> job_of((size_t)n_pairs, -1);
+    std::vector<int> job_of;
     size_t stage_bytes = 0;
-    if (q_host && nq_host > 0) {
-        stage_bytes = (size_t)nq_host * LCM_DESC_BYTES;
-        rc = ensure_pinned(h->h_pair_stage, h->h_pair_stage_bytes, stage_bytes + 65536 + (size_t)n_pairs * 2048); if (rc) return rc;
-        memcpy(h->h_pair_stage, q_host, stage_bytes);
-    }
-    for (int p = 0; p < n_pairs; ++p) {
-        RowSrc q{}, t{};
-        if (q_host) { q.host = q_host; q.n = nq_host; }
-        else { rc = stored_src(h, pairs[p].query_frame_id, &q, nullptr); if (rc) return rc; }
-        rc = stored_src(h, q_host ? train_ids[p] : pairs[p].train_frame_id, &t, nullptr); if (rc) return rc;
-        if (q.n == 0 || t.n == 0) continue;                     // BFMatcher: an empty side => no matches
-        job_of[(size_t)p] = (int)jobs.size();
-        jobs.push_back({q.dev ? (uint32_t)((size_t)(q.dev - h->d_rows) / LCM_DESC_BYTES) : 0u, q.n,
-                        (uint32_t)((size_t)(t.dev - h->d_rows) / LCM_DESC_BYTES), t.n});
-    }
-    rc = wait_db(h); if (rc) return rc;
-    if ((size_t)h->cap_frames * (size_t)h->stride_rows >= 0xFFFFFFFFull)
-        return fail(LCM_ERR_CAPACITY, "the database arena exceeds 2^32 rows: pair items address rows with 32 bits");
+    rc = batch_jobs(h, q_host, nq_host, pairs, train_ids, n_pairs, jobs, job_of, &stage_bytes); if (rc) return rc;
     const uint32_t* keys = nullptr;
     std::vector<size_t> row0;
     rc = run_pair_jobs(h, h->d_rows, h->d_rows, q_host != nullptr, false, stage_bytes, jobs, &keys, row0); if (rc) return rc;
