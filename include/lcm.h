@@ -20,6 +20,9 @@
  *   lcm_detect_loops      <- LoopClosingSystem::detectLoops (include/loop_closing.hpp:48)
  *   lcm_all_vs_all        <- the O(N^2) "every frame against every frame >= gap ago" search, whose only
  *                            executed analogue in the tree is src/main.cpp:1375-1388
+ *   lcm_all_vs_all_ratio  <- that loop with the score it actually uses: the number of ratio-test survivors of
+ *                            matchFeatures(desc[curr], desc[past], matches, 0.7) per pair (src/main.cpp:1386-1387);
+ *                            lcm_query_scores_ratio is its one-frame form
  *   lcm_loop_candidate    <- struct LoopCandidate (include/loop_closing.hpp:22-27), same field order
  *   lcm_dmatch            <- cv::DMatch as consumed at src/main.cpp:551-555 (queryIdx, trainIdx, imgIdx, distance)
  *
@@ -303,6 +306,25 @@ LCM_API int  lcm_all_vs_all_argmin(lcm_handle* h, const void* d_query_rows, cons
 LCM_API int  lcm_all_vs_all_loops(lcm_handle* h, const void* d_query_rows, const int32_t* d_query_counts,
                                   const int32_t* q_ids, const int32_t* q_keypoints, int n_q_frames, int q_stride_rows,
                                   lcm_loop_candidate* out, size_t cap, size_t* n_out, size_t* n_pairs_out);
+/* lcm_all_vs_all with the reference's loop-search score (src/main.cpp:1375-1388): per pair, good_count = number of query
+ * rows whose best neighbour passes best.distance < ratio * second.distance (knnMatch(k = 2) order, strict, IEEE double;
+ * a row without a second neighbour does not count), min_dist = min over query rows of the best distance, n_train as usual.
+ * The second neighbour's distance is the second smallest distance counted with multiplicity (two train rows tied at the
+ * minimum: second == best); one stored row: good_count = 0; an empty side: good_count = 0, min_dist = 0xFFFF.  Pair set,
+ * order, pair_offsets, the sizing call and the external query set are those of lcm_all_vs_all.  lcm_params.ratio,
+ * dist_floor, min_matches and sim_threshold are not consulted, nor is the kernel variant: one vector-ALU kernel keeps every
+ * query row's two smallest distances and counts on the device (route LCM_ROUTE_PLAIN).  The reference's `rows < 100`
+ * skip and its `>= 300` threshold stay with the caller, on the records and the frames' row counts.
+ * LCM_ERR_INVALID_ARG while cross_check != 0 and for a NaN or negative ratio, as the k = 2 pair calls; LCM_ERR_CAPACITY
+ * for a query frame above 2048 rows (there is no packed route here) and for a too-small scores_cap (nothing written). */
+LCM_API int  lcm_all_vs_all_ratio(lcm_handle* h, const void* d_query_rows, const int32_t* d_query_counts,
+                                  const int32_t* q_ids, int n_q_frames, int q_stride_rows, double ratio,
+                                  void* d_scores, size_t scores_cap, size_t* n_pairs, size_t* pair_offsets);
+/* lcm_query_scores with the same score: one host query frame against every stored frame with id gap >= min_gap.
+ * Synchronous; ordered after every append issued so far; online tickets in flight are not disturbed.  out_scores /
+ * out_frame_ids need room for lcm_db_size() records. */
+LCM_API int  lcm_query_scores_ratio(lcm_handle* h, const uint8_t* query, int nq, int query_frame_id, double ratio,
+                                    lcm_score* out_scores, int32_t* out_frame_ids, int* n_out);
 LCM_API int  lcm_last_launch_info(const lcm_handle* h, lcm_launch_info* info);
 /* Device address and record count of the score array the last lcm_all_vs_all_loops left in HBM (same order as
  * lcm_all_vs_all would write; valid until the next bulk call on this handle; NULL / 0 if there is none). */

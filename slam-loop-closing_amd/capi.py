@@ -131,6 +131,9 @@ _SIGNATURES = {
                                          C.POINTER(C.c_size_t), _vp]),
     "lcm_all_vs_all_loops": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_size_t,
                                         C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "lcm_all_vs_all_ratio": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp, C.c_size_t,
+                                        C.POINTER(C.c_size_t), _vp]),
+    "lcm_query_scores_ratio": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp, _i32p]),
     "lcm_last_launch_info": (C.c_int, [_vp, C.POINTER(LaunchInfo)]),
     "lcm_last_bulk_scores": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "lcm_set_kernel_variant": (C.c_int, [_vp, C.c_int]),
@@ -424,6 +427,18 @@ class Matcher:
                                           ids.ctypes.data_as(_vp), C.byref(n)))
         return scores[: n.value], ids[: n.value]
 
+    def query_scores_ratio(self, query, query_frame_id: int, ratio: float) -> Tuple[np.ndarray, np.ndarray]:
+        """query_scores with good_count = number of rows that pass Lowe's ratio test (knnMatch(k=2), best < ratio *
+        second) against each eligible stored frame: (records, stored frame ids)."""
+        q = _rows(query)
+        cap = max(len(self), 1)
+        scores = np.zeros(cap, SCORE_DTYPE)
+        ids = np.zeros(cap, np.int32)
+        n = C.c_int32(0)
+        _check(self._lib.lcm_query_scores_ratio(self._h, _ptr(q), q.shape[0], query_frame_id, ratio,
+                                                scores.ctypes.data_as(_vp), ids.ctypes.data_as(_vp), C.byref(n)))
+        return scores[: n.value], ids[: n.value]
+
     def query_submit(self, query, query_frame_id: int) -> int:
         """Asynchronous query: returns a ticket at once (the rows are copied before returning)."""
         q = _rows(query)
@@ -528,6 +543,30 @@ class Matcher:
                                                _vp(d_query_counts) if d_query_counts else None, _ptr(ids), nq,
                                                q_stride_rows, _vp(d_scores), scores_cap, _vp(d_index_sums),
                                                C.byref(n), None))
+        return n.value
+
+    def all_vs_all_ratio_plan(self, ratio: float, d_query_rows: int = 0, d_query_counts: int = 0,
+                              q_ids: Optional[Sequence[int]] = None, q_stride_rows: int = 0) -> Tuple[int, np.ndarray]:
+        """Sizing call of all_vs_all_ratio: returns (n_pairs, offsets[n_q_frames + 1])."""
+        ids = None if q_ids is None else np.ascontiguousarray(q_ids, np.int32)
+        nq = len(self) if ids is None else ids.shape[0]
+        offs = np.zeros(nq + 1, np.uintp)
+        n = C.c_size_t(0)
+        _check(self._lib.lcm_all_vs_all_ratio(self._h, _vp(d_query_rows) if d_query_rows else None,
+                                              _vp(d_query_counts) if d_query_counts else None, _ptr(ids), nq,
+                                              q_stride_rows, ratio, None, 0, C.byref(n), offs.ctypes.data_as(_vp)))
+        return n.value, offs
+
+    def all_vs_all_ratio(self, ratio: float, d_scores: int, scores_cap: int, d_query_rows: int = 0,
+                         d_query_counts: int = 0, q_ids: Optional[Sequence[int]] = None, q_stride_rows: int = 0) -> int:
+        """all_vs_all with the reference's loop-search score: good_count = number of query rows that pass Lowe's ratio
+        test (knnMatch(k=2), best < ratio * second).  Enqueued on the handle's stream; records land at d_scores."""
+        ids = None if q_ids is None else np.ascontiguousarray(q_ids, np.int32)
+        nq = len(self) if ids is None else ids.shape[0]
+        n = C.c_size_t(0)
+        _check(self._lib.lcm_all_vs_all_ratio(self._h, _vp(d_query_rows) if d_query_rows else None,
+                                              _vp(d_query_counts) if d_query_counts else None, _ptr(ids), nq,
+                                              q_stride_rows, ratio, _vp(d_scores), scores_cap, C.byref(n), None))
         return n.value
 
     def all_vs_all_loops(self, cap: int = 1 << 20, d_query_rows: int = 0, d_query_counts: int = 0,

@@ -219,6 +219,7 @@ void lcm_destroy(lcm_handle* h) {
     (void)hipFree(h->d_rows); (void)hipFree(h->d_counts);
     (void)hipFree(h->d_keys); (void)hipFree(h->plan.d_items); (void)hipFree(h->plan.d_pk_tab);
     (void)hipFree(h->d_bulk_scores); (void)hipFree(h->d_meta); (void)hipFree(h->d_cands);
+    (void)hipFree(h->ratio_plan.d_items); (void)hipFree(h->d_ratio_q); (void)hipFree(h->d_ratio_scores);
     for (QuerySlot& q : h->qslots) {
         (void)hipFree(q.d_query); (void)hipFree(q.d_scores); (void)hipFree(q.d_dist); (void)hipFree(q.d_meta);
         if (q.h_meta) (void)hipHostFree(q.h_meta);

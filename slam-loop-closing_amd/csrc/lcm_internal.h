@@ -4,6 +4,7 @@
 //   lcm_bulk.cpp       bulk all-vs-all, fused loops   lcm_cross.cpp    cross_check scoring
 //   lcm_mfma_host.cpp  opt-in matrix-core variants    lcm_group.cpp    multi-GPU group (RCCL)
 //   lcm_knn.cpp        pair mode with k = 2 neighbours + Lowe's ratio test
+//   lcm_ratio.cpp      bulk / online loop search scored with Lowe's ratio test
 // Not installed; the public surface is include/lcm.h.
 #pragma once
 #include "../../include/lcm.h"
@@ -215,6 +216,12 @@ struct lcm_handle {
     lcm_online_stats online{};         // totals over collected online queries (lcm_online_stats_read)
     uint64_t db_generation = 1;        // bumped whenever stored frames are dropped (lcm_db_clear / lcm_db_load)
     Plan plan;
+    // lcm_all_vs_all_ratio / lcm_query_scores_ratio (lcm_ratio.cpp): a plan and buffers of their own.  The plan is always
+    // in the plain form and is reused only when its whole signature compares equal, so nothing has to invalidate it and
+    // it never meets `plan` (packed chunks, scratch): the two searches alternate freely on one handle.
+    Plan ratio_plan;
+    uint8_t* d_ratio_q = nullptr; size_t d_ratio_q_bytes = 0;          // the online call's query rows
+    lcm_score* d_ratio_scores = nullptr; size_t d_ratio_scores_n = 0;  // ... and its records
     lcm_launch_info info{};
     bool info_pending = false;
 };

@@ -153,6 +153,31 @@ hipError_t launch_knn2_pairs_small(const Knn2Args& a, uint32_t n_items, hipStrea
 // GLOBAL train indices, final_keys[(out_row0 + r) * 2 + {0, 1}] (seg_keys: chunk_rows key PAIRS per item).
 hipError_t launch_fold_pair_keys2(const FoldArgs& a, uint32_t max_nq, hipStream_t st);
 
+// ---- bulk / online loop search scored with Lowe's ratio test (lcm_ratio.hip): src/main.cpp:1375-1388 -------------------
+// One workgroup = one WorkItem (or an implicit run of stored slots for ONE query frame, as ScoreArgs' implicit items):
+// per pair, good_count = number of query rows with best < ratio * second (knnMatch(k = 2) order, the second smallest
+// distance counted with multiplicity; a row without a second neighbour does not count), min_dist = min of the best
+// distances, n_train; the record layout is k_score_rowlane's.  The ratio test is the table lookup d1 < lim[d2]:
+// lim[d2] = number of integers d1 in 0..256 with (double)d1 < ratio * (double)d2, built by the host.
+constexpr int RATIO_LIM_ENTRIES = 258;          // d2 = 0..256, + one zero entry that "no second neighbour" is clamped to
+struct RatioArgs {
+    const uint32_t* q_rows;      // query frames: frame f at q_rows + f * q_stride_words, rows of 8 dwords
+    const int32_t*  q_counts;    // rows per query frame (items != NULL)
+    uint32_t        q_stride_words;
+    const uint32_t* db_rows;     // stored frames, same layout, padded as the TRAIN role needs
+    const int32_t*  db_counts;
+    uint32_t        db_stride_words;
+    const WorkItem* items;       // NULL => implicit: workgroup b = query frame 0 (imp_nq rows) against stored slots
+                                 // [b * imp_spi, min((b + 1) * imp_spi, imp_total)), records at scores[slot]
+    void*           scores;      // lcm_score records (8 bytes each)
+    uint32_t        imp_spi, imp_total;
+    int32_t         imp_nq;
+    uint16_t        lim[RATIO_LIM_ENTRIES];
+};
+// max_query_rows = largest row count of any query frame referenced (<= MAX_FUSED_QUERY_ROWS): picks the workgroup shape
+// (64 / 128 / 192 / 256 threads of 8 rows per lane), as launch_score does.
+hipError_t launch_score_ratio(const RatioArgs& a, uint32_t n_items, int max_query_rows, hipStream_t st);
+
 // On-device loop test over a finished score array (BASELINE.json configs[3] "fused on-device filter + loop test"):
 // pair p belongs to query frame c = upper_bound(offsets, p) - 1 and stored slot p - offsets[c]; a candidate is
 // similarity = good / min(kp_q, kp_t) > sim_threshold (IEEE double, strict) and good >= min_matches.  Candidates
