@@ -23,6 +23,11 @@
  *   lcm_all_vs_all_ratio  <- that loop with the score it actually uses: the number of ratio-test survivors of
  *                            matchFeatures(desc[curr], desc[past], matches, 0.7) per pair (src/main.cpp:1386-1387);
  *                            lcm_query_scores_ratio is its one-frame form
+ *   lcm_ratio_loop_test   <- that loop's verdict: `allDescriptors[i].rows < 100` skips a pair (src/main.cpp:1382),
+ *                            `matches.size() >= 300` accepts the pair (:1388); ratio and both thresholds are parameters
+ *   lcm_all_vs_all_loops_ratio <- the whole loop (src/main.cpp:1375-1388) in one call: ratio-test scores + that verdict on
+ *                            the device, only candidates cross PCIe; lcm_detect_loops_ratio is its one-frame form
+ *   lcm_group_all_vs_all_ratio, lcm_group_all_vs_all_loops_ratio <- the same two searches over several devices
  *   lcm_loop_candidate    <- struct LoopCandidate (include/loop_closing.hpp:22-27), same field order
  *   lcm_dmatch            <- cv::DMatch as consumed at src/main.cpp:551-555 (queryIdx, trainIdx, imgIdx, distance)
  *
@@ -325,6 +330,50 @@ LCM_API int  lcm_all_vs_all_ratio(lcm_handle* h, const void* d_query_rows, const
  * out_frame_ids need room for lcm_db_size() records. */
 LCM_API int  lcm_query_scores_ratio(lcm_handle* h, const uint8_t* query, int nq, int query_frame_id, double ratio,
                                     lcm_score* out_scores, int32_t* out_frame_ids, int* n_out);
+
+/* ---- the reference's own loop rule on the ratio-test score (src/main.cpp:1379-1388) ----------------------------------- */
+/* A pair (current frame c, stored frame s, id_c - id_s >= min_gap) is a loop candidate iff
+ *     rows_c >= min_rows  &&  rows_s >= min_rows          (src/main.cpp:1382: `allDescriptors[..].rows < 100` -> continue)
+ *     &&  good_count(c, s, ratio) >= min_matches          (src/main.cpp:1386-1388: matches.size() < 300 -> continue)
+ * with good_count exactly what lcm_all_vs_all_ratio writes and rows the DESCRIPTOR row counts (not keypoint counts).
+ * Defaults (lcm_ratio_loop_params_default): ratio 0.7, min_rows 100, min_matches 300 — the reference's literals.  The
+ * candidate is the usual lcm_loop_candidate: num_matches = good_count, similarity_score = (double)good_count /
+ * (double)min(rows_c, rows_s) in IEEE double (0.0 when min_rows = 0 admits an empty side) — informational, not part of the
+ * verdict.  lcm_params.ratio / dist_floor / min_matches / sim_threshold, keypoint counts and the kernel variant play no
+ * part; min_gap (on ids) plays its usual one — the reference's loopGap = max(3, numViews / 2) is the caller's
+ * lcm_set_params.  `poses[i].R.empty()` (src/main.cpp:1377, :1381) stays with the caller: do not append such frames, or
+ * drop their candidates.
+ * Shared by the calls below: rp == NULL means the defaults; LCM_ERR_INVALID_ARG for a NaN or negative ratio, a negative
+ * min_rows or min_matches, and while cross_check != 0 (as the other k = 2 calls); LCM_ERR_CAPACITY for a query frame above
+ * 2048 rows (as lcm_all_vs_all_ratio) and for more candidates than `cap` (or out == NULL with candidates present): *n_out
+ * is then the count and nothing is written, as lcm_all_vs_all_loops behaves.  Candidates come out in (current id,
+ * matched id) ascending order without a host sort. */
+typedef struct lcm_ratio_loop_params {
+    double  ratio;          /* Lowe's ratio of the score                          src/main.cpp:1386 (0.7) */
+    int32_t min_rows;       /* both frames need >= min_rows descriptor rows       src/main.cpp:1382 (100) */
+    int32_t min_matches;    /* loop needs good_count >= min_matches               src/main.cpp:1388 (300) */
+} lcm_ratio_loop_params;    /* 16 bytes */
+LCM_API void lcm_ratio_loop_params_default(lcm_ratio_loop_params* p);
+/* Host-only verdict on a shipped record (no device needed): rows_train = s->n_train.  Returns 1 if the pair is a loop
+ * candidate; *similarity (optional) as above.  p == NULL: the defaults. */
+LCM_API int  lcm_ratio_loop_test(const lcm_ratio_loop_params* p, const lcm_score* s, int rows_query, double* similarity);
+/* lcm_all_vs_all_ratio with that verdict fused on the device: pair set, external query set and *n_pairs_out are
+ * lcm_all_vs_all_ratio's; the score array stays in device memory (afterwards lcm_last_bulk_scores returns it, byte for byte
+ * what lcm_all_vs_all_ratio writes for the same input), verdict and ordered compaction run on the device
+ * (k_ratio_loop_count, k_block_scan, k_ratio_loop_emit: aux_kernel_ms of lcm_last_launch_info; route, kernel_ms, pairs and
+ * distances as the ratio search reports them) and only the candidates cross PCIe.  Pairs with a frame below min_rows are
+ * still scored (the score array does not depend on rp->min_rows). */
+LCM_API int  lcm_all_vs_all_loops_ratio(lcm_handle* h, const void* d_query_rows, const int32_t* d_query_counts,
+                                        const int32_t* q_ids, int n_q_frames, int q_stride_rows,
+                                        const lcm_ratio_loop_params* rp, lcm_loop_candidate* out, size_t cap,
+                                        size_t* n_out, size_t* n_pairs_out);
+/* The one-frame form (one trip of the loop at src/main.cpp:1375): query != NULL gives the current frame from the host, as
+ * lcm_query_scores_ratio takes it; query == NULL means the STORED frame with id current_frame_id (nq is ignored), whose
+ * rows are used in place in the arena — LCM_ERR_NOT_FOUND if it is not stored.  Synchronous; outstanding online tickets
+ * are not disturbed.  The verdict over the at most lcm_db_size() records runs on the host (lcm_ratio_loop_test). */
+LCM_API int  lcm_detect_loops_ratio(lcm_handle* h, int current_frame_id, const uint8_t* query, int nq,
+                                    const lcm_ratio_loop_params* rp, lcm_loop_candidate* out, int cap, int* n_out);
+
 LCM_API int  lcm_last_launch_info(const lcm_handle* h, lcm_launch_info* info);
 /* Device address and record count of the score array the last lcm_all_vs_all_loops left in HBM (same order as
  * lcm_all_vs_all would write; valid until the next bulk call on this handle; NULL / 0 if there is none). */
@@ -412,6 +461,16 @@ LCM_API int  lcm_group_all_vs_all_argmin(lcm_group* g, lcm_score* out_scores, ui
  * own PCIe link, all links at once — and are merged on the host into (current id, matched id) order.  *n_out = number
  * found (LCM_ERR_CAPACITY if > cap, nothing written); *n_pairs_out (optional) = pairs scored. */
 LCM_API int  lcm_group_all_vs_all_loops(lcm_group* g, lcm_loop_candidate* out, size_t cap, size_t* n_out, size_t* n_pairs_out);
+/* lcm_all_vs_all_ratio over the group, under lcm_group_all_vs_all's contract: the same records in the same order as a
+ * single handle holding all frames (a group of ONE: byte for byte), arena all-gather skipped when nothing was appended,
+ * lcm_group_info filled as usual; on RCCL, peer-copy and loopback groups alike.  LCM_ERR_INVALID_ARG for a NaN or negative
+ * ratio and while cross_check != 0. */
+LCM_API int  lcm_group_all_vs_all_ratio(lcm_group* g, double ratio, lcm_score* out_scores, size_t cap, size_t* n_pairs,
+                                        size_t* pair_offsets);
+/* lcm_all_vs_all_loops_ratio over the group, under lcm_group_all_vs_all_loops' contract: every shard applies the verdict
+ * to its own records on its own device, only candidates leave the devices, W-way merged on the host. */
+LCM_API int  lcm_group_all_vs_all_loops_ratio(lcm_group* g, const lcm_ratio_loop_params* rp, lcm_loop_candidate* out,
+                                              size_t cap, size_t* n_out, size_t* n_pairs_out);
 LCM_API int  lcm_group_last_info(const lcm_group* g, lcm_group_info* info);
 /* lcm_query_scores / lcm_detect_loops over all shards (query uploaded to every device; per-shard records interleaved
  * on the host: a few KB per query). */

@@ -49,6 +49,11 @@ class LoopCandidate(C.Structure):
                 ("similarity_score", C.c_double)]
 
 
+class RatioLoopParams(C.Structure):
+    """lcm_ratio_loop_params: the reference's loop rule on the ratio-test score (src/main.cpp:1379-1388)."""
+    _fields_ = [("ratio", C.c_double), ("min_rows", C.c_int32), ("min_matches", C.c_int32)]
+
+
 class LaunchInfo(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("pairs", C.c_uint64), ("distances", C.c_uint64),
                 ("algo_bytes", C.c_uint64), ("launches", C.c_uint32), ("workgroups", C.c_uint32),
@@ -134,6 +139,11 @@ _SIGNATURES = {
     "lcm_all_vs_all_ratio": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_double, _vp, C.c_size_t,
                                         C.POINTER(C.c_size_t), _vp]),
     "lcm_query_scores_ratio": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp, _i32p]),
+    "lcm_ratio_loop_params_default": (None, [C.POINTER(RatioLoopParams)]),
+    "lcm_ratio_loop_test": (C.c_int, [C.POINTER(RatioLoopParams), C.POINTER(Score), C.c_int, C.POINTER(C.c_double)]),
+    "lcm_all_vs_all_loops_ratio": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(RatioLoopParams), _vp,
+                                              C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "lcm_detect_loops_ratio": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.POINTER(RatioLoopParams), _vp, C.c_int, _i32p]),
     "lcm_last_launch_info": (C.c_int, [_vp, C.POINTER(LaunchInfo)]),
     "lcm_last_bulk_scores": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "lcm_set_kernel_variant": (C.c_int, [_vp, C.c_int]),
@@ -159,6 +169,9 @@ _SIGNATURES = {
     "lcm_group_all_vs_all": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t), _vp]),
     "lcm_group_all_vs_all_argmin": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t), _vp]),
     "lcm_group_all_vs_all_loops": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "lcm_group_all_vs_all_ratio": (C.c_int, [_vp, C.c_double, _vp, C.c_size_t, C.POINTER(C.c_size_t), _vp]),
+    "lcm_group_all_vs_all_loops_ratio": (C.c_int, [_vp, C.POINTER(RatioLoopParams), _vp, C.c_size_t, C.POINTER(C.c_size_t),
+                                                    C.POINTER(C.c_size_t)]),
     "lcm_group_query_submit_batch": (C.c_int, [_vp, _vp, _i32p, _i32p, C.c_int, _i32p]),
     "lcm_group_query_collect_batch": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_size_t), _vp]),
     "lcm_group_online_stats_read": (C.c_int, [_vp, C.POINTER(OnlineStats), C.c_int]),
@@ -205,6 +218,38 @@ def default_params() -> Params:
     p = Params()
     load_library().lcm_params_default(C.byref(p))
     return p
+
+
+def default_ratio_loop_params() -> RatioLoopParams:
+    p = RatioLoopParams()
+    load_library().lcm_ratio_loop_params_default(C.byref(p))
+    return p
+
+
+def _ratio_loop_params(ratio, min_rows, min_matches) -> Optional[RatioLoopParams]:
+    """None (the library's defaults: rp == NULL) when all three are None, else a structure with the given values over
+    the defaults."""
+    if ratio is None and min_rows is None and min_matches is None:
+        return None
+    p = default_ratio_loop_params()
+    if ratio is not None:
+        p.ratio = ratio
+    if min_rows is not None:
+        p.min_rows = min_rows
+    if min_matches is not None:
+        p.min_matches = min_matches
+    return p
+
+
+def ratio_loop_test(score, rows_query: int, ratio: Optional[float] = None, min_rows: Optional[int] = None,
+                    min_matches: Optional[int] = None) -> Tuple[bool, float]:
+    """lcm_ratio_loop_test (host-only, no device needed): (is a loop candidate, similarity) of one shipped record; the
+    stored frame's row count is the record's n_train.  Parameters left at None: 0.7 / 100 / 300."""
+    s = Score(int(score["good_count"]), int(score["min_dist"]), int(score["n_train"]))
+    p = _ratio_loop_params(ratio, min_rows, min_matches)
+    sim = C.c_double(0)
+    r = load_library().lcm_ratio_loop_test(None if p is None else C.byref(p), C.byref(s), rows_query, C.byref(sim))
+    return bool(r), sim.value
 
 
 def _rows(a) -> np.ndarray:
@@ -587,6 +632,48 @@ class Matcher:
                                               q_stride_rows, out.ctypes.data_as(_vp), cap, C.byref(n), C.byref(npairs)))
         return out[: n.value], npairs.value
 
+    def all_vs_all_loops_ratio(self, ratio: Optional[float] = None, min_rows: Optional[int] = None,
+                               min_matches: Optional[int] = None, cap: int = 1 << 20, d_query_rows: int = 0,
+                               d_query_counts: int = 0, q_ids: Optional[Sequence[int]] = None, q_stride_rows: int = 0,
+                               out: Optional[np.ndarray] = None) -> Tuple[np.ndarray, int]:
+        """The reference's loop search (src/main.cpp:1375-1388) in one call: ratio-test scores + `rows >= min_rows` on both
+        frames + `good_count >= min_matches`, decided and compacted on the device: (candidates sorted by (current,
+        matched), n_pairs).  ratio / min_rows / min_matches left at None: 0.7 / 100 / 300 (all three None: rp = NULL)."""
+        rp = _ratio_loop_params(ratio, min_rows, min_matches)
+        ids = None if q_ids is None else np.ascontiguousarray(q_ids, np.int32)
+        nq = len(self) if ids is None else ids.shape[0]
+        if out is None:
+            out = np.zeros(max(cap, 1), CANDIDATE_DTYPE)
+        else:
+            assert out.dtype == CANDIDATE_DTYPE and out.flags["C_CONTIGUOUS"]
+            cap = len(out)
+        n, npairs = C.c_size_t(0), C.c_size_t(0)
+        _check(self._lib.lcm_all_vs_all_loops_ratio(self._h, _vp(d_query_rows) if d_query_rows else None,
+                                                    _vp(d_query_counts) if d_query_counts else None, _ptr(ids), nq,
+                                                    q_stride_rows, None if rp is None else C.byref(rp),
+                                                    out.ctypes.data_as(_vp), cap, C.byref(n), C.byref(npairs)))
+        return out[: n.value], npairs.value
+
+    def detect_loops_ratio(self, current_frame_id: int, query=None, ratio: Optional[float] = None,
+                           min_rows: Optional[int] = None, min_matches: Optional[int] = None,
+                           cap: Optional[int] = None) -> np.ndarray:
+        """One frame of all_vs_all_loops_ratio: `query` (host rows), or the stored frame with that id (query=None, its
+        rows used in place on the device), against every eligible stored frame."""
+        rp = _ratio_loop_params(ratio, min_rows, min_matches)
+        cap = max(len(self), 1) if cap is None else cap
+        out = np.zeros(max(cap, 1), CANDIDATE_DTYPE)
+        n = C.c_int32(0)
+        if query is None:
+            qp, nq = None, 0
+        else:
+            q = _rows(query)
+            nq = q.shape[0]
+            # an explicit empty frame still needs a non-NULL pointer to be told apart from "use the stored frame"
+            qp = q.ctypes.data_as(_vp) if nq else np.zeros((1, DESC_BYTES), np.uint8).ctypes.data_as(_vp)
+        _check(self._lib.lcm_detect_loops_ratio(self._h, current_frame_id, qp, nq, None if rp is None else C.byref(rp),
+                                                out.ctypes.data_as(_vp), cap, C.byref(n)))
+        return out[: n.value]
+
     def last_bulk_scores(self) -> np.ndarray:
         """Download the score records the last all_vs_all_loops call left on the device."""
         p, n = _vp(), C.c_size_t(0)
@@ -713,6 +800,28 @@ class Group:
         out = np.zeros(max(n.value, 1), SCORE_DTYPE)
         _check(self._lib.lcm_group_all_vs_all(self._g, out.ctypes.data_as(_vp), len(out), C.byref(n), None))
         return out[: n.value], offs
+
+    def all_vs_all_ratio(self, ratio: float) -> Tuple[np.ndarray, np.ndarray]:
+        """all_vs_all with the ratio-test score (lcm_group_all_vs_all_ratio): (merged scores, offsets[len + 1])."""
+        n = C.c_size_t(0)
+        offs = np.zeros(len(self) + 1, np.uintp)
+        _check(self._lib.lcm_group_all_vs_all_ratio(self._g, ratio, None, 0, C.byref(n), offs.ctypes.data_as(_vp)))
+        out = np.zeros(max(n.value, 1), SCORE_DTYPE)
+        _check(self._lib.lcm_group_all_vs_all_ratio(self._g, ratio, out.ctypes.data_as(_vp), len(out), C.byref(n), None))
+        return out[: n.value], offs
+
+    def all_vs_all_loops_ratio(self, ratio: Optional[float] = None, min_rows: Optional[int] = None,
+                               min_matches: Optional[int] = None, cap: int = 1 << 20,
+                               out: Optional[np.ndarray] = None) -> Tuple[np.ndarray, int]:
+        """(loop candidates of the reference's rule in (current, matched) order, pairs scored) —
+        lcm_group_all_vs_all_loops_ratio; parameters as Matcher.all_vs_all_loops_ratio."""
+        rp = _ratio_loop_params(ratio, min_rows, min_matches)
+        if out is None:
+            out = np.zeros(max(cap, 1), CANDIDATE_DTYPE)
+        n, npairs = C.c_size_t(0), C.c_size_t(0)
+        _check(self._lib.lcm_group_all_vs_all_loops_ratio(self._g, None if rp is None else C.byref(rp), out.ctypes.data_as(_vp),
+                                                          len(out), C.byref(n), C.byref(npairs)))
+        return out[: n.value], npairs.value
 
     def truncate(self, n_frames: int):
         _check(self._lib.lcm_group_truncate(self._g, n_frames))

@@ -463,27 +463,9 @@ int loop_test_device(lcm_handle* h, const void* d_scores, size_t n_pairs, const 
     a.block_counts = d_counter + 4;
     a.n_q = (uint32_t)n_q; a.n_pairs = (uint32_t)n_pairs; a.cap = 0;
     a.min_matches = h->params.min_matches; a.sim_threshold = h->params.sim_threshold;
-    HIP_TRY(hipEventRecord(h->ev_aux_start, h->stream));
-    hipError_t e = lcm::launch_loop_count(a, h->stream);
-    if (e != hipSuccess) return fail(LCM_ERR_HIP, "loop-test kernel launch failed: %s", hipGetErrorString(e));
-    uint32_t found = 0;
-    HIP_TRY(hipMemcpyAsync(&found, d_counter, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));          // also: `meta` (pageable) has been consumed
-    *n_found = found;
-    if (found > cap) {
-        HIP_TRY(hipEventRecord(h->ev_aux_stop, h->stream));
-        h->aux_pending = true;
-        return fail(LCM_ERR_CAPACITY, "%u loop candidates but room for %zu", found, cap);
-    }
-    if (found) {
-        rc = ensure_dev(h->d_cands, h->d_cands_n, (size_t)found); if (rc) return rc;
-        a.out = h->d_cands; a.cap = found;
-        e = lcm::launch_loop_emit(a, h->stream);
-        if (e != hipSuccess) return fail(LCM_ERR_HIP, "loop-test kernel launch failed: %s", hipGetErrorString(e));
-    }
-    HIP_TRY(hipEventRecord(h->ev_aux_stop, h->stream));
-    h->aux_pending = true;
-    return LCM_OK;
+    return count_then_emit(h, d_counter, cap, n_found,
+                           [&] { return lcm::launch_loop_count(a, h->stream); },
+                           [&](lcm_loop_candidate* out, uint32_t n) { a.out = out; a.cap = n; return lcm::launch_loop_emit(a, h->stream); });
 }
 
 }  // namespace lcm

@@ -541,12 +541,15 @@ int lcm_group_load(lcm_group* g, const char* path) {
 
 namespace {
 
-enum SearchMode { SEARCH_SCORES = 0, SEARCH_ARGMIN = 1, SEARCH_LOOPS = 2 };
+enum SearchMode { SEARCH_SCORES = 0, SEARCH_ARGMIN = 1, SEARCH_LOOPS = 2, SEARCH_RATIO_SCORES = 3, SEARCH_RATIO_LOOPS = 4 };
 
 // The bulk search of a group, in its three forms (score records; + per-pair index checksums through the argmin kernel;
-// loop test on every shard's device, only candidates leave the devices).
+// loop test on every shard's device, only candidates leave the devices) and the ratio-test scored twins of the first and
+// the last (lcm::all_vs_all_ratio per shard; rp: ratio + the reference's thresholds, checked by the caller — only its
+// ratio is read in the scores form).
 int group_search(lcm_group* g, SearchMode mode, lcm_score* out_scores, uint32_t* out_isums, size_t cap, size_t* n_pairs,
-                 size_t* pair_offsets, lcm_loop_candidate* out_cands, size_t cand_cap, size_t* n_cands) {
+                 size_t* pair_offsets, lcm_loop_candidate* out_cands, size_t cand_cap, size_t* n_cands,
+                 const lcm_ratio_loop_params* rp = nullptr) {
     const int W = g->world;
     const int N = (int)g->frames.size();
     // ---- bookkeeping: merged offsets, per-shard per-query offsets
@@ -556,7 +559,9 @@ int group_search(lcm_group* g, SearchMode mode, lcm_score* out_scores, uint32_t*
     { const int rc0 = shard_layout(g->frames, W, g->params.min_gap, offs, offr, total); if (rc0) return rc0; }
     *n_pairs = (size_t)total;
     if (pair_offsets) for (int c = 0; c <= N; ++c) pair_offsets[c] = offs[(size_t)c];
-    if (mode != SEARCH_LOOPS) {
+    const bool ratio = mode == SEARCH_RATIO_SCORES || mode == SEARCH_RATIO_LOOPS;
+    const bool loops = mode == SEARCH_LOOPS || mode == SEARCH_RATIO_LOOPS;
+    if (!loops) {
         if (!out_scores) return LCM_OK;                     // sizing call
         if (cap < total) return fail(LCM_ERR_CAPACITY, "scores buffer holds %zu records, need %llu", cap, (unsigned long long)total);
     }
@@ -632,7 +637,6 @@ int group_search(lcm_group* g, SearchMode mode, lcm_score* out_scores, uint32_t*
         q_frame_of[(size_t)p] = (uint32_t)((p % W) * shard_cap + p / W);
     }
     const bool argmin = mode == SEARCH_ARGMIN;
-    const bool loops = mode == SEARCH_LOOPS;
     int rc = set_dev(g, 0); if (rc) return rc;
     if (!loops) {
         // device 0's shard is written straight into the gather buffer (it is the first segment)
@@ -657,8 +661,10 @@ int group_search(lcm_group* g, SearchMode mode, lcm_score* out_scores, uint32_t*
         void* dst = (r == 0 && !loops) ? (void*)g->d_gather : (void*)g->d_scores[(size_t)r];
         uint32_t* dsum = !argmin ? nullptr : (r == 0 ? g->d_gather_idx : g->d_isums[(size_t)r]);
         size_t n = 0;
-        int rc2 = lcm::all_vs_all(h, g->d_qrows[(size_t)r], g->d_qcounts[(size_t)r], ids.data(), N, stride, dst, want, &n, nullptr, dsum,
-                                  q_frame_of.data(), counts.data());
+        int rc2 = ratio ? lcm::all_vs_all_ratio(h, g->d_qrows[(size_t)r], g->d_qcounts[(size_t)r], ids.data(), N, stride, rp->ratio, dst, want,
+                                                &n, nullptr, q_frame_of.data(), counts.data())
+                        : lcm::all_vs_all(h, g->d_qrows[(size_t)r], g->d_qcounts[(size_t)r], ids.data(), N, stride, dst, want, &n, nullptr, dsum,
+                                          q_frame_of.data(), counts.data());
         if (rc2) return rc2;
         if (n != want) return fail(LCM_ERR_HIP, "scored %zu pairs, expected %zu", n, want);
         if (!loops || want == 0) return LCM_OK;
@@ -666,8 +672,10 @@ int group_search(lcm_group* g, SearchMode mode, lcm_score* out_scores, uint32_t*
         std::vector<int32_t> oid, okp;
         for (int p = r; p < N; p += W) { oid.push_back(ids[(size_t)p]); okp.push_back(kps[(size_t)p]); }
         size_t found = 0;
-        rc2 = lcm::loop_test_device(h, dst, want, offr[(size_t)r].data(), N, ids.data(), kps.data(), (int)oid.size(), oid.data(), okp.data(),
-                                    out_cands ? cand_cap : 0, &found);
+        rc2 = ratio ? lcm::ratio_loop_test_device(h, dst, want, offr[(size_t)r].data(), N, ids.data(), counts.data(), (int)oid.size(), oid.data(),
+                                                  *rp, out_cands ? cand_cap : 0, &found)
+                    : lcm::loop_test_device(h, dst, want, offr[(size_t)r].data(), N, ids.data(), kps.data(), (int)oid.size(), oid.data(), okp.data(),
+                                            out_cands ? cand_cap : 0, &found);
         shard_found[(size_t)r] = found;
         if (rc2 == LCM_ERR_CAPACITY) { shard_over[(size_t)r] = 1; return LCM_OK; }     // the caller sums the counts and reports
         if (rc2) return rc2;
@@ -794,6 +802,33 @@ int lcm_group_all_vs_all_loops(lcm_group* g, lcm_loop_candidate* out, size_t cap
     *n_out = 0;
     size_t n_pairs = 0;
     const int rc = guarded([&] { return group_search(g, SEARCH_LOOPS, nullptr, nullptr, 0, &n_pairs, nullptr, out, cap, n_out); });
+    if (n_pairs_out) *n_pairs_out = n_pairs;
+    return rc;
+}
+
+// what every k = 2 call refuses, before any shard is touched
+static int group_check_ratio(const lcm_group* g, const lcm_ratio_loop_params* rp_in, lcm_ratio_loop_params* rp) {
+    const int rc = lcm::ratio_loop_params_checked(rp_in, rp); if (rc) return rc;
+    if (g->params.cross_check != 0) return fail(LCM_ERR_INVALID_ARG, "ratio-test scoring needs cross_check = 0 (BFMatcher: knn == 1 under crossCheck)");
+    return LCM_OK;
+}
+
+int lcm_group_all_vs_all_ratio(lcm_group* g, double ratio, lcm_score* out_scores, size_t cap, size_t* n_pairs, size_t* pair_offsets) {
+    if (!g || !n_pairs) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+    lcm_ratio_loop_params rp;
+    lcm_ratio_loop_params_default(&rp);
+    rp.ratio = ratio;
+    const int rc = group_check_ratio(g, &rp, &rp); if (rc) return rc;
+    return guarded([&] { return group_search(g, SEARCH_RATIO_SCORES, out_scores, nullptr, cap, n_pairs, pair_offsets, nullptr, 0, nullptr, &rp); });
+}
+
+int lcm_group_all_vs_all_loops_ratio(lcm_group* g, const lcm_ratio_loop_params* rp_in, lcm_loop_candidate* out, size_t cap, size_t* n_out, size_t* n_pairs_out) {
+    if (!g || !n_out) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+    *n_out = 0;
+    lcm_ratio_loop_params rp;
+    int rc = group_check_ratio(g, rp_in, &rp); if (rc) return rc;
+    size_t n_pairs = 0;
+    rc = guarded([&] { return group_search(g, SEARCH_RATIO_LOOPS, nullptr, nullptr, 0, &n_pairs, nullptr, out, cap, n_out, &rp); });
     if (n_pairs_out) *n_pairs_out = n_pairs;
     return rc;
 }

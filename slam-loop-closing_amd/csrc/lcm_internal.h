@@ -251,6 +251,34 @@ int ensure_pinned(T*& p, size_t& have, size_t need) {
     return LCM_OK;
 }
 
+// The host sequence of an on-device loop test (lcm::loop_test_device, lcm::ratio_loop_test_device), between the two aux
+// events: count() enqueues the count + scan kernels, the count is read back, a too-small `cap` is refused (*n_found set)
+// BEFORE anything proportional to the count is allocated, then emit(out, n) enqueues the kernel that writes the n
+// candidates to h->d_cands.  Everything on h's stream; the stream is synchronised once, after the count.
+template <typename Count, typename Emit>
+int count_then_emit(lcm_handle* h, const uint32_t* d_counter, size_t cap, size_t* n_found, Count&& count, Emit&& emit) {
+    HIP_TRY(hipEventRecord(h->ev_aux_start, h->stream));
+    hipError_t e = count();
+    if (e != hipSuccess) return fail(LCM_ERR_HIP, "loop-test kernel launch failed: %s", hipGetErrorString(e));
+    uint32_t found = 0;
+    HIP_TRY(hipMemcpyAsync(&found, d_counter, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));          // also: the caller's metadata upload (pageable) has been consumed
+    *n_found = found;
+    if (found > cap) {
+        HIP_TRY(hipEventRecord(h->ev_aux_stop, h->stream));
+        h->aux_pending = true;
+        return fail(LCM_ERR_CAPACITY, "%u loop candidates but room for %zu", found, cap);
+    }
+    if (found) {
+        const int rc = ensure_dev(h->d_cands, h->d_cands_n, (size_t)found); if (rc) return rc;
+        e = emit(h->d_cands, found);
+        if (e != hipSuccess) return fail(LCM_ERR_HIP, "loop-test kernel launch failed: %s", hipGetErrorString(e));
+    }
+    HIP_TRY(hipEventRecord(h->ev_aux_stop, h->stream));
+    h->aux_pending = true;
+    return LCM_OK;
+}
+
 }  // namespace
 
 namespace lcm {
@@ -284,6 +312,19 @@ int all_vs_all(lcm_handle* h, const void* d_query_rows, const int32_t* d_query_c
 int loop_test_device(lcm_handle* h, const void* d_scores, size_t n_pairs, const uint32_t* offsets, int n_q,
                      const int32_t* q_ids, const int32_t* q_kp, int n_db, const int32_t* db_ids, const int32_t* db_kp,
                      size_t cap, size_t* n_found);
+// ---- lcm_ratio.cpp
+// Bulk search behind lcm_all_vs_all_ratio; q_frame_of / h_query_counts as in all_vs_all above (the group's shards).
+int all_vs_all_ratio(lcm_handle* h, const void* d_query_rows, const int32_t* d_query_counts, const int32_t* q_ids,
+                     int n_q_frames, int q_stride_rows, double ratio, void* d_scores, size_t scores_cap, size_t* n_pairs,
+                     size_t* pair_offsets, const uint32_t* q_frame_of, const int32_t* h_query_counts);
+// NULL -> the defaults; LCM_ERR_INVALID_ARG for a NaN or negative ratio, a negative min_rows or min_matches
+int ratio_loop_params_checked(const lcm_ratio_loop_params* rp, lcm_ratio_loop_params* out);
+// The reference's loop rule (src/main.cpp:1379-1388) + ordered compaction over a ratio score array on h's device: the twin
+// of loop_test_device, with descriptor row counts of the query frames in place of keypoint counts (the stored frames'
+// come from the records).  On LCM_OK the *n_found candidates are in h->d_cands.
+int ratio_loop_test_device(lcm_handle* h, const void* d_scores, size_t n_pairs, const uint32_t* offsets, int n_q,
+                           const int32_t* q_ids, const int32_t* q_rows, int n_db, const int32_t* db_ids,
+                           const lcm_ratio_loop_params& rp, size_t cap, size_t* n_found);
 // ---- lcm_pair.cpp: the pair mode's plumbing, shared with lcm_knn.cpp.  k = neighbours per query row: 1 (match) or 2
 // (knnMatch(k = 2)); with k = 2 every key array holds 2 keys per query row (best, second; 0xFFFFFFFF = none).
 // Row source: host rows (uploaded to scratch) or rows already on the device (a stored frame).

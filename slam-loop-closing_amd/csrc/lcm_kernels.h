@@ -178,6 +178,29 @@ struct RatioArgs {
 // (64 / 128 / 192 / 256 threads of 8 rows per lane), as launch_score does.
 hipError_t launch_score_ratio(const RatioArgs& a, uint32_t n_items, int max_query_rows, hipStream_t st);
 
+// The reference's own loop rule over a finished ratio score array (src/main.cpp:1379-1388: `rows < 100` skips a frame,
+// matches.size() >= 300 accepts the pair): pair p belongs to query frame c = upper_bound(offsets, p) - 1 and stored slot
+// p - offsets[c], as in LoopTestArgs; a candidate is q_rows[c] >= min_rows && n_train >= min_rows && good >= min_matches
+// (n_train from the record).  The record written is (q_ids[c], db_ids[slot], good, good / min(q_rows[c], n_train)), the
+// division in IEEE double (0.0 when an empty side is admitted by min_rows = 0) and not part of the verdict.  Candidates are
+// compacted in pair order exactly as the loop test above does: k_ratio_loop_count (per 256-pair block), k_block_scan,
+// k_ratio_loop_emit (wave-ballot rank).
+struct RatioLoopArgs {
+    const void*     scores;        // lcm_score records
+    const uint32_t* offsets;       // n_q + 1 pair offsets per query frame
+    const int32_t*  q_ids;         // per query frame
+    const int32_t*  q_rows;        // descriptor rows per query frame
+    const int32_t*  db_ids;        // per stored slot
+    void*           out;           // lcm_loop_candidate records (24 bytes)
+    uint32_t*       counter;       // number of candidates found (may exceed cap: count only)
+    uint32_t*       block_counts;  // scratch: ceil(n_pairs / 256) words (candidates per block, then their prefix)
+    uint32_t        n_q, n_pairs, cap;
+    int32_t         min_rows, min_matches;
+};
+// The same two steps as launch_loop_count / launch_loop_emit.
+hipError_t launch_ratio_loop_count(const RatioLoopArgs& a, hipStream_t st);
+hipError_t launch_ratio_loop_emit(const RatioLoopArgs& a, hipStream_t st);
+
 // On-device loop test over a finished score array (BASELINE.json configs[3] "fused on-device filter + loop test"):
 // pair p belongs to query frame c = upper_bound(offsets, p) - 1 and stored slot p - offsets[c]; a candidate is
 // similarity = good / min(kp_q, kp_t) > sim_threshold (IEEE double, strict) and good >= min_matches.  Candidates
@@ -202,6 +225,9 @@ struct LoopTestArgs {
 // block_counts); launch_loop_emit then writes candidate k < cap to out[k].
 hipError_t launch_loop_count(const LoopTestArgs& a, hipStream_t st);
 hipError_t launch_loop_emit(const LoopTestArgs& a, hipStream_t st);
+// k_block_scan on its own (the ratio loop test in lcm_ratio.hip shares it): counts[0..n) -> exclusive prefix sums in
+// place, *total = their sum.
+hipError_t launch_block_scan(uint32_t* counts, uint32_t n, uint32_t* total, hipStream_t st);
 
 // Cross-check (lcm_params.cross_check, BFMatcher crossCheck = true): per pair, forward keys (every query row's first
 // nearest train row) and backward keys (every train row's first nearest query row) -> the pair's score record.

@@ -934,6 +934,11 @@ hipError_t launch_loop_count(const LoopTestArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
+hipError_t launch_block_scan(uint32_t* counts, uint32_t n, uint32_t* total, hipStream_t st) {
+    hipLaunchKernelGGL(k_block_scan, dim3(1), dim3(1024), 0, st, counts, n, total);
+    return hipGetLastError();
+}
+
 hipError_t launch_loop_emit(const LoopTestArgs& a, hipStream_t st) {
     if (a.n_pairs == 0) return hipSuccess;
     hipLaunchKernelGGL(k_loop_emit, dim3((a.n_pairs + 255) / 256), dim3(256), 0, st, a);

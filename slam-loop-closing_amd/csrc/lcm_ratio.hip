@@ -194,4 +194,68 @@ hipError_t launch_score_ratio(const RatioArgs& a, uint32_t n_items, int max_quer
     return hipErrorInvalidValue;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The reference's loop rule (src/main.cpp:1379-1388) over the finished score array, candidates compacted IN PAIR ORDER =
+// (current id, matched id) ascending, as k_loop_count / k_block_scan / k_loop_emit do for README.md:123-126
+// (lcm_kernels.hip): verdict per pair + candidates per 256-pair block, exclusive prefix of the block counts (the SAME
+// k_block_scan), verdict again + rank inside the block by wave ballots + write.  The division is IEEE double (no
+// fast-math), so the record equals the host's lcm_ratio_loop_test bit for bit.  HBM-bound: 2 x 8 bytes read per pair (+ one
+// cached row count) + 24 bytes written per candidate.
+// ---------------------------------------------------------------------------------------------------
+struct RatioCandidateRec { int32_t cur, matched, num; int32_t pad; double sim; };
+static_assert(sizeof(RatioCandidateRec) == 24, "lcm_loop_candidate layout");
+
+__device__ __forceinline__ bool ratio_loop_verdict(const RatioLoopArgs& a, uint32_t p, RatioCandidateRec& r) {
+    if (p >= a.n_pairs) return false;
+    // query frame of pair p: last c with offsets[c] <= p
+    uint32_t lo = 0, hi = a.n_q;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (a.offsets[mid] <= p) lo = mid; else hi = mid;
+    }
+    const uint32_t c = lo, slot = p - a.offsets[c];
+    const uint2 rec = reinterpret_cast<const uint2*>(a.scores)[p];
+    const uint32_t good = rec.x;
+    const int rows_c = a.q_rows[c], rows_s = (int)(rec.y >> 16);
+    if (rows_c < a.min_rows || rows_s < a.min_rows || (int64_t)good < (int64_t)a.min_matches) return false;
+    const int den = min(rows_c, rows_s);
+    r.cur = a.q_ids[c]; r.matched = a.db_ids[slot]; r.num = (int32_t)good; r.pad = 0;
+    r.sim = den > 0 ? (double)good / (double)den : 0.0;
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_ratio_loop_count(RatioLoopArgs a) {
+    RatioCandidateRec r;
+    const bool pass = ratio_loop_verdict(a, blockIdx.x * 256u + threadIdx.x, r);
+    const int n = __syncthreads_count(pass ? 1 : 0);
+    if (threadIdx.x == 0) a.block_counts[blockIdx.x] = (uint32_t)n;
+}
+
+__global__ __launch_bounds__(256) void k_ratio_loop_emit(RatioLoopArgs a) {
+    __shared__ uint32_t wave_n[4];
+    RatioCandidateRec r;
+    const bool pass = ratio_loop_verdict(a, blockIdx.x * 256u + threadIdx.x, r);
+    const uint64_t m = __ballot(pass);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) wave_n[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (!pass) return;
+    uint32_t k = a.block_counts[blockIdx.x] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) k += wave_n[w];
+    if (k < a.cap) reinterpret_cast<RatioCandidateRec*>(a.out)[k] = r;
+}
+
+hipError_t launch_ratio_loop_count(const RatioLoopArgs& a, hipStream_t st) {
+    if (a.n_pairs == 0) return hipSuccess;
+    const uint32_t n_blocks = (a.n_pairs + 255) / 256;
+    hipLaunchKernelGGL(k_ratio_loop_count, dim3(n_blocks), dim3(256), 0, st, a);
+    return launch_block_scan(a.block_counts, n_blocks, a.counter, st);
+}
+
+hipError_t launch_ratio_loop_emit(const RatioLoopArgs& a, hipStream_t st) {
+    if (a.n_pairs == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_ratio_loop_emit, dim3((a.n_pairs + 255) / 256), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
 }  // namespace lcm
