@@ -29,6 +29,8 @@
  *                            the device, only candidates cross PCIe; lcm_detect_loops_ratio is its one-frame form
  *   lcm_group_all_vs_all_ratio, lcm_group_all_vs_all_loops_ratio <- the same two searches over several devices
  *   lcm_loop_candidate    <- struct LoopCandidate (include/loop_closing.hpp:22-27), same field order
+ *   lcm_knn2_pair_l2, lcm_match_features_ratio_l2, lcm_match_pairs_ratio_l2 <- the same matcher on what the reference
+ *                            feeds it: 128-D cv::SIFT rows under cv::NORM_L2 (src/main.cpp:497-504, :517)
  *   lcm_dmatch            <- cv::DMatch as consumed at src/main.cpp:551-555 (queryIdx, trainIdx, imgIdx, distance)
  *
  * Conventions
@@ -255,6 +257,41 @@ LCM_API int  lcm_match_stored_batch_ratio(lcm_handle* h, const lcm_pair_ref* pai
 /* ... and one query frame given by the host (the current frame, src/main.cpp:1386's desc1) against n_trains stored frames. */
 LCM_API int  lcm_match_query_batch_ratio(lcm_handle* h, const uint8_t* query, int nq, const int32_t* train_frame_ids, int n_trains,
                                          double ratio, lcm_dmatch* out, size_t cap, size_t* offsets);
+
+/* ---- pair mode on SIFT rows: BFMatcher(NORM_L2, crossCheck=false).knnMatch(k = 2) + Lowe's ratio test ------------ */
+/* What the reference's matcher is fed: detectAndDescribeSIFT (src/main.cpp:497-504, cv::SIFT::create(4000)) produces
+ * 128-D descriptors and cv::BFMatcher(cv::NORM_L2, false) (:517) matches them.  OpenCV's SIFT stores every element through
+ * saturate_cast<uchar>, so a row is 128 integers 0..255 (SIFT::create(..., CV_8U) hands out the bytes themselves): a row
+ * here is LCM_SIFT_BYTES uint8.  With D(q, t) = sum (q_i - t_i)^2, an exact integer <= 8 323 200 < 2^24, the distance is
+ * s = (float)sqrt(D), correctly rounded — bit for bit what OpenCV's float accumulation + sqrt give — and a query row's
+ * neighbours are the two smallest (s, train index) pairs, best first (batchDistance, K = 2).  The order is on s, not on D:
+ * above 2^22 adjacent integers can share a float root (first 4197200, 4197201) and the lower train index then comes first.
+ * `best` is kept iff (double)s1 < ratio * (double)s2 (strict); a row with fewer than two neighbours is dropped.
+ * Shared with the Hamming k = 2 calls above: LCM_ERR_INVALID_ARG while cross_check != 0, for a NaN or negative ratio, a
+ * NULL pointer or a negative count; LCM_ERR_CAPACITY when `cap` is too small, checked before anything is written to `out`;
+ * lcm_params.ratio / dist_floor play no part; the work is ordered on the handle's stream and finished on return.  A matrix
+ * holds at most 65 535 rows (LCM_ERR_CAPACITY above).  Nothing is stored: the 32-byte database is a different descriptor. */
+#define LCM_SIFT_BYTES 128
+/* Host only, no device needed: n CV_32F SIFT rows (src/main.cpp:497-504) -> bytes.  LCM_ERR_INVALID_ARG, and nothing
+ * written, if any value is not an integer in [0, 255] (NaN, inf, fractions, RootSIFT-normalised rows). */
+LCM_API int  lcm_sift_pack_f32(const float* rows, int n, uint8_t* out);
+/* knnMatch(k = 2) (src/main.cpp:517-520): train_idx[2*q + k] and dist[2*q + k] are required, dist_sq[2*q + k] (= D) is
+ * optional and may be NULL.  A missing second neighbour (nt == 1) is train_idx = -1, dist = +INFINITY, dist_sq = 0xFFFFFFFF.
+ * *n_neighbours = min(nt, 2), or 0 with nothing written if either side is empty. */
+LCM_API int  lcm_knn2_pair_l2(lcm_handle* h, const uint8_t* query, int nq, const uint8_t* train, int nt,
+                              int32_t* train_idx, float* dist, uint32_t* dist_sq, int* n_neighbours);
+/* matchFeatures(desc1, desc2, good, ratio) (src/main.cpp:509-534; :1154 calls it with 0.75).  `out` needs room for nq
+ * records.  Each record has img_idx = 0 and distance = s1. */
+LCM_API int  lcm_match_features_ratio_l2(lcm_handle* h, const uint8_t* query, int nq, const uint8_t* train, int nt, double ratio,
+                                         lcm_dmatch* out, int* n_out);
+/* The loop search's inner call for MANY pairs (src/main.cpp:1375-1388): n_frames host matrices (frames[f]: rows[f] rows),
+ * each uploaded ONCE; pairs[p] = {query position, train position} into `frames` (a position outside [0, n_frames) is
+ * LCM_ERR_INVALID_ARG; a pair may name the same matrix on both sides; a pair with an empty side has an empty list).  One
+ * score launch plus one fold for the whole set.  The lists come back to back in `out`, bounded by offsets[n_pairs + 1]
+ * (required); the match count the reference thresholds at 300 (:1388) is offsets[p+1] - offsets[p]. */
+LCM_API int  lcm_match_pairs_ratio_l2(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_frames,
+                                      const lcm_pair_ref* pairs, int n_pairs, double ratio,
+                                      lcm_dmatch* out, size_t cap, size_t* offsets);
 
 /* ---- loop search against the stored database --------------------------------------------------------- */
 /* Score `query` (id query_frame_id) against every stored frame with query_frame_id - id >= min_gap, ascending

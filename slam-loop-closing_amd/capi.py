@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # LCM_LIB_PATH: test plumbing only (e.g. the host-sanitizer build of the same sources, `make -C csrc asan`)
 LIB_PATH = os.environ.get("LCM_LIB_PATH") or os.path.join(_HERE, "lib", "liblcm_hip.so")
 DESC_BYTES = 32
+SIFT_BYTES = 128          # a SIFT row: 128 uint8 (pair mode under L2)
 KEY_SHIFT = 22
 TUNE_ITEM_SLOTS, TUNE_ONLINE_SPLIT, TUNE_PACKED, TUNE_ONLINE_STREAMS, TUNE_PACKED_SCRATCH_MB = 0, 1, 2, 3, 4      # lcm_tuning
 TUNE_PAIR_UPLOAD_KERNEL, TUNE_PAIR_HOST_FOLD = 5, 6
@@ -122,6 +123,10 @@ _SIGNATURES = {
     "lcm_match_stored_ratio": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, _vp, C.c_int, _i32p]),
     "lcm_match_stored_batch_ratio": (C.c_int, [_vp, _vp, C.c_int, C.c_double, _vp, C.c_size_t, _vp]),
     "lcm_match_query_batch_ratio": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_double, _vp, C.c_size_t, _vp]),
+    "lcm_sift_pack_f32": (C.c_int, [_vp, C.c_int, _vp]),
+    "lcm_knn2_pair_l2": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _i32p]),
+    "lcm_match_features_ratio_l2": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_double, _vp, _i32p]),
+    "lcm_match_pairs_ratio_l2": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_double, _vp, C.c_size_t, _vp]),
     "lcm_query_scores": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _i32p]),
     "lcm_query_submit": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _i32p]),
     "lcm_query_collect": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i32p]),
@@ -261,6 +266,30 @@ def _rows(a) -> np.ndarray:
 
 def _ptr(a: Optional[np.ndarray]):
     return None if a is None or a.size == 0 else a.ctypes.data_as(_vp)
+
+
+def _sift_rows(a) -> np.ndarray:
+    a = np.asarray(a)
+    if a.dtype != np.uint8:
+        raise ValueError(f"SIFT rows must be uint8 (sift_pack_f32 converts CV_32F rows), got {a.dtype}")
+    a = np.ascontiguousarray(a)
+    if a.ndim != 2 or a.shape[1] != SIFT_BYTES:
+        raise ValueError(f"SIFT matrix must be (n, {SIFT_BYTES}) uint8, got {a.shape}")
+    return a
+
+
+def sift_pack_f32(rows) -> np.ndarray:
+    """lcm_sift_pack_f32 (host only, no device needed): CV_32F SIFT rows (n, 128) -> uint8 (n, 128).  LcmError
+    (ERR_INVALID_ARG) if any value is not an integer in [0, 255]."""
+    a = np.asarray(rows)
+    if a.dtype != np.float32:
+        raise ValueError(f"expected float32 rows, got {a.dtype}")
+    a = np.ascontiguousarray(a)
+    if a.ndim != 2 or a.shape[1] != SIFT_BYTES:
+        raise ValueError(f"SIFT matrix must be (n, {SIFT_BYTES}) float32, got {a.shape}")
+    out = np.zeros(a.shape, np.uint8)
+    _check(load_library().lcm_sift_pack_f32(_ptr(a), a.shape[0], _ptr(out)))
+    return out
 
 
 class Matcher:
@@ -459,6 +488,49 @@ class Matcher:
         offs = np.zeros(n + 1, np.uintp)
         _check(self._lib.lcm_match_query_batch_ratio(self._h, _ptr(q), q.shape[0], _ptr(ids), n, ratio,
                                                      out.ctypes.data_as(_vp), cap, offs.ctypes.data_as(_vp)))
+        return [out[int(offs[i]): int(offs[i + 1])] for i in range(n)], offs
+
+    # -- pair mode on SIFT rows (128 uint8, L2): knnMatch(k=2) + Lowe's ratio test ------------------
+    sift_pack_f32 = staticmethod(sift_pack_f32)
+
+    def knn2_pair_l2(self, query, train) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """BFMatcher(NORM_L2).knnMatch(k=2) on SIFT rows: (train_idx int32[nq, 2], dist float32[nq, 2], dist_sq
+        uint32[nq, 2]), best first; a missing second neighbour (one train row) is (-1, inf, 0xFFFFFFFF); nq = 0 rows if
+        either side is empty."""
+        q, t = _sift_rows(query), _sift_rows(train)
+        idx = np.empty((q.shape[0], 2), np.int32)
+        dist = np.empty((q.shape[0], 2), np.float32)
+        dsq = np.empty((q.shape[0], 2), np.uint32)
+        n = C.c_int32(0)
+        _check(self._lib.lcm_knn2_pair_l2(self._h, _ptr(q), q.shape[0], _ptr(t), t.shape[0], _ptr(idx), _ptr(dist), _ptr(dsq),
+                                          C.byref(n)))
+        rows = q.shape[0] if n.value else 0
+        return idx[:rows], dist[:rows], dsq[:rows]
+
+    def match_features_ratio_l2(self, query, train, ratio: float) -> np.ndarray:
+        """matchFeatures(desc1, desc2, good, ratio) on SIFT rows -> DMatch records, query order."""
+        q, t = _sift_rows(query), _sift_rows(train)
+        out = np.zeros(max(q.shape[0], 1), DMATCH_DTYPE)
+        n = C.c_int32(0)
+        _check(self._lib.lcm_match_features_ratio_l2(self._h, _ptr(q), q.shape[0], _ptr(t), t.shape[0], ratio,
+                                                     out.ctypes.data_as(_vp), C.byref(n)))
+        return out[: n.value]
+
+    def match_pairs_ratio_l2(self, frames: Sequence[np.ndarray], pairs: Sequence[Tuple[int, int]], ratio: float,
+                             cap: Optional[int] = None):
+        """Ratio-filtered match lists of many (query position, train position) pairs into `frames` (SIFT matrices, each
+        uploaded once) in one launch: (list of DMatch arrays, offsets[n + 1])."""
+        fr = [_sift_rows(f) for f in frames]
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n = pr.shape[0]
+        ptrs = (_vp * max(len(fr), 1))(*[f.ctypes.data if f.size else None for f in fr])
+        rows = np.array([f.shape[0] for f in fr] or [0], np.int32)
+        if cap is None:
+            cap = sum(fr[q].shape[0] for q in pr[:, 0] if 0 <= q < len(fr))
+        out = np.zeros(max(cap, 1), DMATCH_DTYPE)
+        offs = np.zeros(n + 1, np.uintp)
+        _check(self._lib.lcm_match_pairs_ratio_l2(self._h, C.cast(ptrs, _vp), rows.ctypes.data_as(_vp), len(fr), _ptr(pr), n,
+                                                  ratio, out.ctypes.data_as(_vp), cap, offs.ctypes.data_as(_vp)))
         return [out[int(offs[i]): int(offs[i + 1])] for i in range(n)], offs
 
     # -- loop search -------------------------------------------------------------------------------

@@ -220,6 +220,9 @@ void lcm_destroy(lcm_handle* h) {
     (void)hipFree(h->d_keys); (void)hipFree(h->plan.d_items); (void)hipFree(h->plan.d_pk_tab);
     (void)hipFree(h->d_bulk_scores); (void)hipFree(h->d_meta); (void)hipFree(h->d_cands);
     (void)hipFree(h->ratio_plan.d_items); (void)hipFree(h->d_ratio_q); (void)hipFree(h->d_ratio_scores);
+    (void)hipFree(h->l2.d_raw); (void)hipFree(h->l2.d_img); (void)hipFree(h->l2.d_tw); (void)hipFree(h->l2.d_tab);
+    (void)hipFree(h->l2.d_seg); (void)hipFree(h->l2.d_fin); (void)hipFree(h->l2.d_flag);
+    if (h->l2.h_fin) (void)hipHostFree(h->l2.h_fin);
     for (QuerySlot& q : h->qslots) {
         (void)hipFree(q.d_query); (void)hipFree(q.d_scores); (void)hipFree(q.d_dist); (void)hipFree(q.d_meta);
         if (q.h_meta) (void)hipHostFree(q.h_meta);

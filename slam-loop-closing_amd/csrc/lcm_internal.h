@@ -5,6 +5,7 @@
 //   lcm_mfma_host.cpp  opt-in matrix-core variants    lcm_group.cpp    multi-GPU group (RCCL)
 //   lcm_knn.cpp        pair mode with k = 2 neighbours + Lowe's ratio test
 //   lcm_ratio.cpp      bulk / online loop search scored with Lowe's ratio test
+//   lcm_l2.cpp         pair mode on 128-byte SIFT rows under L2 (knnMatch(k = 2) + ratio test)
 // Not installed; the public surface is include/lcm.h.
 #pragma once
 #include "../../include/lcm.h"
@@ -222,6 +223,18 @@ struct lcm_handle {
     Plan ratio_plan;
     uint8_t* d_ratio_q = nullptr; size_t d_ratio_q_bytes = 0;          // the online call's query rows
     lcm_score* d_ratio_scores = nullptr; size_t d_ratio_scores_n = 0;  // ... and its records
+    // pair mode on SIFT rows (lcm_l2.cpp): raw rows, operand image and per-row words of the call's matrices in the tile
+    // space, the tables, per-item keys, folded results (device + pinned landing zone), the rescan's flag list
+    struct L2Scratch {
+        uint8_t* d_raw = nullptr;  size_t d_raw_n = 0;
+        uint8_t* d_img = nullptr;  size_t d_img_n = 0;
+        uint32_t* d_tw = nullptr;  size_t d_tw_n = 0;
+        uint8_t* d_tab = nullptr;  size_t d_tab_n = 0;
+        uint2* d_seg = nullptr;    size_t d_seg_n = 0;
+        uint4* d_fin = nullptr;    size_t d_fin_n = 0;
+        uint2* d_flag = nullptr;   size_t d_flag_n = 0;
+        uint4* h_fin = nullptr;    size_t h_fin_n = 0;
+    } l2;
     lcm_launch_info info{};
     bool info_pending = false;
 };

@@ -153,6 +153,52 @@ hipError_t launch_knn2_pairs_small(const Knn2Args& a, uint32_t n_items, hipStrea
 // GLOBAL train indices, final_keys[(out_row0 + r) * 2 + {0, 1}] (seg_keys: chunk_rows key PAIRS per item).
 hipError_t launch_fold_pair_keys2(const FoldArgs& a, uint32_t max_nq, hipStream_t st);
 
+// ---- pair mode on SIFT rows (lcm_l2.hip): BFMatcher(NORM_L2).knnMatch(k = 2) over 128-byte rows, src/main.cpp:497-534 ----
+// Matrices live back to back in a TILE space: a matrix starts at a multiple of 32 rows, tile T covers raw rows
+// [32 T, 32 T + 32) of `raw`, its operand image is img + T * 4096 and its per-row words are tw + 32 T.
+constexpr int L2_ROW_BYTES = 128;
+constexpr int L2_TILE_ROWS = 32;
+constexpr int L2_TILE_BYTES = 4096;
+constexpr int L2_SEG_ROWS = 512;                    // train rows per item: the key's index field
+constexpr int L2_KEY_SHIFT = 9;                     // packed key = D << 9 | segment-local train index (D < 2^23)
+constexpr uint32_t L2_RESCAN_MIN = 1u << 22;        // sqrtf is injective on integers below this
+struct L2PackArgs {
+    const uint8_t*  raw;         // uint8 rows as uploaded
+    const uint32_t* tile_meta;   // per tile: rows of the tile that exist (1..32) | index of the tile inside its matrix << 8
+    uint8_t*        img;         // int8 (byte ^ 0x80) in the MFMA's operand order, pad rows zero
+    uint32_t*       tw;          // per row: sum of the squared int8 << 9 | row index inside its 512-row segment
+    uint32_t        n_tiles;
+};
+hipError_t launch_l2_pack(const L2PackArgs& a, hipStream_t st);
+// One workgroup = one item: q_rows <= chunk_rows query rows starting at tile q_tile against t_rows <= 512 train rows starting
+// at tile t_tile.  Per (item, query row) the two smallest keys -> seg_keys[item * chunk_rows + row], 0xFFFFFFFF = none.
+struct L2Item { uint32_t q_tile, q_rows, t_tile, t_rows; };
+struct L2ScoreArgs {
+    const uint8_t*  img;
+    const uint32_t* tw;
+    const L2Item*   items;
+    uint2*          seg_keys;
+    uint32_t        chunk_rows;  // 128 (one query tile per wave) or 256 (two)
+};
+hipError_t launch_l2_score(const L2ScoreArgs& a, uint32_t n_items, hipStream_t st);
+// One job = one (query matrix, train matrix) pair: its items are first_item + chunk * n_seg + segment.  The fold writes
+// (D1, idx1, D2, idx2) per query row (0xFFFFFFFF = none) to final_keys[out_row0 + row] and appends the rows whose D2 is
+// >= L2_RESCAN_MIN to `flagged` (job, row), counted in *counter (zeroed by the caller); the rescan redoes those rows in
+// (sqrtf(D), index) order over the raw bytes.
+struct L2Job { uint32_t q_tile, nq, t_tile, nt, first_item, n_seg, out_row0, reserved; };
+struct L2FoldArgs {
+    const uint2*    seg_keys;
+    uint32_t        chunk_rows;
+    const L2Job*    jobs;
+    uint4*          final_keys;
+    uint32_t*       counter;
+    uint2*          flagged;
+    uint32_t        flag_cap;
+    const uint8_t*  raw;
+};
+hipError_t launch_l2_fold(const L2FoldArgs& a, uint32_t n_jobs, uint32_t max_nq, hipStream_t st);
+hipError_t launch_l2_rescan(const L2FoldArgs& a, hipStream_t st);
+
 // ---- bulk / online loop search scored with Lowe's ratio test (lcm_ratio.hip): src/main.cpp:1375-1388 -------------------
 // One workgroup = one WorkItem (or an implicit run of stored slots for ONE query frame, as ScoreArgs' implicit items):
 // per pair, good_count = number of query rows with best < ratio * second (knnMatch(k = 2) order, the second smallest

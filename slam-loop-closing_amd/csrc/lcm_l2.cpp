@@ -1,0 +1,268 @@
+// lcm_l2.cpp — pair mode on SIFT rows (128 uint8, L2): knnMatch(k = 2) + Lowe's ratio test as the reference runs them on
+// cv::SIFT descriptors (src/main.cpp:497-504, :509-534, :1154, :1375-1388).  The kernels are lcm_l2.hip's; this file
+// lays the matrices out in the tile space, plans the (query chunk x train segment) items, turns the shipped integer
+// squared distances into OpenCV's float distances (sqrtf, correctly rounded on the host) and runs the ratio test in IEEE
+// double.  Part of liblcm_hip.so's host side (C ABI in include/lcm.h); shared state and helpers: lcm_internal.h.
+#include "lcm_internal.h"
+
+#include <cmath>
+#include <limits>
+
+namespace {
+
+constexpr uint32_t NONE = 0xFFFFFFFFu;      // D / index of a neighbour that does not exist
+constexpr int TILE = lcm::L2_TILE_ROWS, SEG = lcm::L2_SEG_ROWS, ROW = LCM_SIFT_BYTES;
+static_assert(LCM_SIFT_BYTES == lcm::L2_ROW_BYTES, "row size");
+
+struct L2Pair { int q, t; };                // positions into the call's matrices, both sides non-empty
+
+// What every k = 2 call refuses (lcm_knn.cpp's rule)
+int check_knn(const lcm_handle* h, double ratio) {
+    if (h->params.cross_check != 0) return fail(LCM_ERR_INVALID_ARG, "k = 2 matching needs cross_check = 0 (BFMatcher: knn == 1 under crossCheck)");
+    if (std::isnan(ratio) || ratio < 0.0) return fail(LCM_ERR_INVALID_ARG, "ratio must be a number >= 0");
+    return LCM_OK;
+}
+
+int check_rows(int n) {
+    if (n < 0) return fail(LCM_ERR_INVALID_ARG, "negative row count");
+    if (n > MAX_FRAME_ROWS) return fail(LCM_ERR_CAPACITY, "a SIFT matrix holds at most %d rows", MAX_FRAME_ROWS);
+    return LCM_OK;
+}
+
+// Query chunk of an item: 128 rows (one tile per wave: twice the workgroups, the latency shape) while the call has few
+// items, else 256 (two tiles per wave share every train fragment: the throughput shape).  LCM_TUNE_L2_CHUNK = 128 | 256
+// pins it (tools/l2_time.py measures both).
+int pick_chunk_rows(const std::vector<L2Pair>& pairs, const int* rows) {
+    if (const char* e = getenv("LCM_TUNE_L2_CHUNK")) { const int v = atoi(e); if (v == 128 || v == 256) return v; }
+    size_t items256 = 0;
+    for (const L2Pair& p : pairs) items256 += (size_t)((rows[p.q] + 255) / 256) * (size_t)((rows[p.t] + SEG - 1) / SEG);
+    return items256 < 1024 ? 128 : 256;
+}
+
+// Uploads every matrix once, packs, scores every pair, folds, rescans: (D1, idx1, D2, idx2) per query row of pair p at
+// (*fin)[4 * (row0[p] + r)], in pinned host memory that stays valid until the next L2 call on this handle.
+int l2_run(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_frames, const std::vector<L2Pair>& pairs,
+           const uint32_t** fin, std::vector<size_t>& row0) {
+    int rc = set_device(h); if (rc) return rc;
+    const size_t P = pairs.size();
+    row0.assign(P + 1, 0);
+    *fin = nullptr;
+    if (P == 0) return LCM_OK;
+
+    // ---- the tile space: matrix f starts at tile tile0[f]
+    std::vector<uint32_t> tile0((size_t)n_frames + 1, 0), tile_meta;
+    for (int f = 0; f < n_frames; ++f) {
+        const uint32_t nt = (uint32_t)((rows[f] + TILE - 1) / TILE);
+        tile0[(size_t)f + 1] = tile0[(size_t)f] + nt;
+        for (uint32_t k = 0; k < nt; ++k) tile_meta.push_back((uint32_t)std::min(TILE, rows[f] - (int)k * TILE) | (k << 8));
+    }
+    const size_t n_tiles = tile_meta.size();
+
+    // ---- items and jobs
+    const int CH = pick_chunk_rows(pairs, rows);
+    std::vector<lcm::L2Item> items;
+    std::vector<lcm::L2Job> jobs(P);
+    size_t total_rows = 0;
+    int max_nq = 0;
+    uint64_t distances = 0;
+    for (size_t p = 0; p < P; ++p) {
+        const int nq = rows[pairs[p].q], nt = rows[pairs[p].t];
+        const int n_chunks = (nq + CH - 1) / CH, n_seg = (nt + SEG - 1) / SEG;
+        const uint32_t qt = tile0[(size_t)pairs[p].q], tt = tile0[(size_t)pairs[p].t];
+        if (items.size() + (size_t)n_chunks * (size_t)n_seg > 0x7FFFFFFFull || total_rows + (size_t)nq > 0x7FFFFFFFull)
+            return fail(LCM_ERR_CAPACITY, "too many pairs for one call");
+        jobs[p] = {qt, (uint32_t)nq, tt, (uint32_t)nt, (uint32_t)items.size(), (uint32_t)n_seg, (uint32_t)total_rows, 0};
+        for (int c = 0; c < n_chunks; ++c)
+            for (int g = 0; g < n_seg; ++g)
+                items.push_back({qt + (uint32_t)(c * (CH / TILE)), (uint32_t)std::min(CH, nq - c * CH),
+                                 tt + (uint32_t)(g * (SEG / TILE)), (uint32_t)std::min(SEG, nt - g * SEG)});
+        row0[p] = total_rows;
+        total_rows += (size_t)nq;
+        max_nq = std::max(max_nq, nq);
+        distances += (uint64_t)nq * (uint64_t)nt;
+    }
+    row0[P] = total_rows;
+    const size_t n_items = items.size();
+
+    // ---- device buffers; the tables go up as one block [tile_meta | items | jobs | counter]
+    auto& s = h->l2;
+    const size_t off_items = (n_tiles * sizeof(uint32_t) + 15) & ~(size_t)15;
+    const size_t off_jobs = off_items + n_items * sizeof(lcm::L2Item);
+    const size_t off_counter = off_jobs + P * sizeof(lcm::L2Job);
+    const size_t tab_bytes = off_counter + 16;
+    std::vector<uint8_t> tab(tab_bytes, 0);
+    memcpy(tab.data(), tile_meta.data(), n_tiles * sizeof(uint32_t));
+    memcpy(tab.data() + off_items, items.data(), n_items * sizeof(lcm::L2Item));
+    memcpy(tab.data() + off_jobs, jobs.data(), P * sizeof(lcm::L2Job));
+    rc = ensure_dev(s.d_raw, s.d_raw_n, n_tiles * (size_t)lcm::L2_TILE_BYTES); if (rc) return rc;
+    rc = ensure_dev(s.d_img, s.d_img_n, n_tiles * (size_t)lcm::L2_TILE_BYTES); if (rc) return rc;
+    rc = ensure_dev(s.d_tw, s.d_tw_n, n_tiles * (size_t)TILE); if (rc) return rc;
+    rc = ensure_dev(s.d_tab, s.d_tab_n, tab_bytes); if (rc) return rc;
+    rc = ensure_dev(s.d_seg, s.d_seg_n, n_items * (size_t)CH); if (rc) return rc;
+    rc = ensure_dev(s.d_fin, s.d_fin_n, total_rows); if (rc) return rc;
+    rc = ensure_dev(s.d_flag, s.d_flag_n, total_rows); if (rc) return rc;
+    rc = ensure_pinned(s.h_fin, s.h_fin_n, total_rows); if (rc) return rc;
+
+    // The sources are pageable: they stay alive (and unchanged) until the synchronisation at the end of this function.
+    for (int f = 0; f < n_frames; ++f)
+        if (rows[f] > 0)
+            HIP_TRY(hipMemcpyAsync(s.d_raw + (size_t)tile0[(size_t)f] * lcm::L2_TILE_BYTES, frames[f], (size_t)rows[f] * ROW,
+                                   hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(s.d_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, h->stream));
+
+    const lcm::L2PackArgs pa{s.d_raw, reinterpret_cast<const uint32_t*>(s.d_tab), s.d_img, s.d_tw, (uint32_t)n_tiles};
+    hipError_t e = lcm::launch_l2_pack(pa, h->stream);
+    if (e != hipSuccess) return fail(LCM_ERR_HIP, "pack kernel launch failed: %s", hipGetErrorString(e));
+    const lcm::L2ScoreArgs sa{s.d_img, s.d_tw, reinterpret_cast<const lcm::L2Item*>(s.d_tab + off_items), s.d_seg, (uint32_t)CH};
+    HIP_TRY(hipEventRecord(h->ev_start, h->stream));
+    e = lcm::launch_l2_score(sa, (uint32_t)n_items, h->stream);
+    if (e != hipSuccess) return fail(LCM_ERR_HIP, "score kernel launch failed: %s", hipGetErrorString(e));
+    HIP_TRY(hipEventRecord(h->ev_stop, h->stream));
+    h->info_pending = true;
+    h->info.workgroups = (uint32_t)n_items; h->info.route = LCM_ROUTE_PLAIN; h->info.launches = 4;
+    h->info.pairs = P; h->info.distances = distances; h->info.algo_bytes = 2 * n_tiles * (uint64_t)lcm::L2_TILE_BYTES + total_rows * 16;
+    const lcm::L2FoldArgs fa{s.d_seg, (uint32_t)CH, reinterpret_cast<const lcm::L2Job*>(s.d_tab + off_jobs), s.d_fin,
+                             reinterpret_cast<uint32_t*>(s.d_tab + off_counter), s.d_flag, (uint32_t)total_rows, s.d_raw};
+    e = lcm::launch_l2_fold(fa, (uint32_t)P, (uint32_t)max_nq, h->stream);
+    if (e != hipSuccess) return fail(LCM_ERR_HIP, "fold kernel launch failed: %s", hipGetErrorString(e));
+    e = lcm::launch_l2_rescan(fa, h->stream);
+    if (e != hipSuccess) return fail(LCM_ERR_HIP, "rescan kernel launch failed: %s", hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(s.h_fin, s.d_fin, total_rows * sizeof(uint4), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    *fin = reinterpret_cast<const uint32_t*>(s.h_fin);
+    return LCM_OK;
+}
+
+inline float dist_of(uint32_t D) { return std::sqrt((float)D); }      // D < 2^24: the conversion is exact, sqrtf correctly rounded
+
+// Lowe's ratio test over one pair's rows (src/main.cpp:524-531): survivors of `s1 < ratio * s2` in double; a row with
+// fewer than two neighbours is dropped.  out == NULL: count only.
+size_t emit_ratio(const uint32_t* fin, int nq, double ratio, lcm_dmatch* out) {
+    size_t k = 0;
+    for (int i = 0; i < nq; ++i) {
+        const uint32_t* r = fin + 4 * (size_t)i;
+        if (r[2] == NONE) continue;
+        const float s1 = dist_of(r[0]), s2 = dist_of(r[2]);
+        if (!((double)s1 < ratio * (double)s2)) continue;
+        if (out) out[k] = lcm_dmatch{i, (int32_t)r[1], 0, s1};
+        ++k;
+    }
+    return k;
+}
+
+int knn2_pair_l2_impl(lcm_handle* h, const uint8_t* query, int nq, const uint8_t* train, int nt, int32_t* train_idx, float* dist,
+                      uint32_t* dist_sq, int* n_neighbours) {
+    if (!h || nq < 0 || nt < 0) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+    if (n_neighbours) *n_neighbours = 0;
+    int rc = check_knn(h, 0.0); if (rc) return rc;
+    rc = check_rows(nq); if (rc) return rc;
+    rc = check_rows(nt); if (rc) return rc;
+    if (nq == 0 || nt == 0) return LCM_OK;
+    if (!query || !train || !train_idx || !dist) return fail(LCM_ERR_INVALID_ARG, "NULL buffer");
+    const uint8_t* frames[2] = {query, train};
+    const int rows[2] = {nq, nt};
+    const uint32_t* fin = nullptr;
+    std::vector<size_t> row0;
+    rc = l2_run(h, frames, rows, 2, {L2Pair{0, 1}}, &fin, row0); if (rc) return rc;
+    for (size_t i = 0; i < (size_t)nq; ++i)
+        for (int k = 0; k < 2; ++k) {
+            const uint32_t D = fin[4 * i + 2 * k], idx = fin[4 * i + 2 * k + 1];
+            const bool none = idx == NONE;
+            train_idx[2 * i + k] = none ? -1 : (int32_t)idx;
+            dist[2 * i + k] = none ? std::numeric_limits<float>::infinity() : dist_of(D);
+            if (dist_sq) dist_sq[2 * i + k] = none ? NONE : D;
+        }
+    if (n_neighbours) *n_neighbours = std::min(nt, 2);
+    return LCM_OK;
+}
+
+int match_features_ratio_l2_impl(lcm_handle* h, const uint8_t* query, int nq, const uint8_t* train, int nt, double ratio,
+                                 lcm_dmatch* out, int* n_out) {
+    if (!h || nq < 0 || nt < 0 || !n_out) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+    *n_out = 0;
+    int rc = check_knn(h, ratio); if (rc) return rc;
+    rc = check_rows(nq); if (rc) return rc;
+    rc = check_rows(nt); if (rc) return rc;
+    if (nq == 0 || nt == 0) return LCM_OK;
+    if (!query || !train || !out) return fail(LCM_ERR_INVALID_ARG, "NULL buffer");
+    const uint8_t* frames[2] = {query, train};
+    const int rows[2] = {nq, nt};
+    const uint32_t* fin = nullptr;
+    std::vector<size_t> row0;
+    rc = l2_run(h, frames, rows, 2, {L2Pair{0, 1}}, &fin, row0); if (rc) return rc;
+    *n_out = (int)emit_ratio(fin, nq, ratio, out);
+    return LCM_OK;
+}
+
+int match_pairs_ratio_l2_impl(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_frames, const lcm_pair_ref* pairs,
+                              int n_pairs, double ratio, lcm_dmatch* out, size_t cap, size_t* offsets) {
+    if (!h || n_frames < 0 || n_pairs < 0 || !offsets || (n_frames > 0 && (!frames || !rows)) || (n_pairs > 0 && !pairs))
+        return fail(LCM_ERR_INVALID_ARG, "bad argument");
+    offsets[0] = 0;
+    int rc = check_knn(h, ratio); if (rc) return rc;
+    for (int f = 0; f < n_frames; ++f) {
+        rc = check_rows(rows[f]); if (rc) return rc;
+        if (rows[f] > 0 && !frames[f]) return fail(LCM_ERR_INVALID_ARG, "matrix %d is NULL", f);
+    }
+    std::vector<L2Pair> live;
+    std::vector<int> job_of((size_t)n_pairs, -1);
+    for (int p = 0; p < n_pairs; ++p) {
+        const int q = pairs[p].query_frame_id, t = pairs[p].train_frame_id;
+        if (q < 0 || q >= n_frames || t < 0 || t >= n_frames) return fail(LCM_ERR_INVALID_ARG, "pair %d: position outside [0, %d)", p, n_frames);
+        if (rows[q] == 0 || rows[t] == 0) continue;
+        job_of[(size_t)p] = (int)live.size();
+        live.push_back(L2Pair{q, t});
+    }
+    const uint32_t* fin = nullptr;
+    std::vector<size_t> row0;
+    rc = l2_run(h, frames, rows, n_frames, live, &fin, row0); if (rc) return rc;
+    // sizes first: a too-small `cap` is refused before anything is written
+    std::vector<size_t> count((size_t)n_pairs, 0);
+    size_t total = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        const int j = job_of[(size_t)p];
+        if (j >= 0) count[(size_t)p] = emit_ratio(fin + 4 * row0[(size_t)j], rows[live[(size_t)j].q], ratio, nullptr);
+        total += count[(size_t)p];
+    }
+    if (total > (out ? cap : 0)) return fail(LCM_ERR_CAPACITY, "%zu matches but the buffer holds %zu records", total, out ? cap : (size_t)0);
+    total = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        offsets[p] = total;
+        const int j = job_of[(size_t)p];
+        if (j >= 0 && count[(size_t)p]) emit_ratio(fin + 4 * row0[(size_t)j], rows[live[(size_t)j].q], ratio, out + total);
+        total += count[(size_t)p];
+    }
+    offsets[n_pairs] = total;
+    return LCM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lcm_sift_pack_f32(const float* rows, int n, uint8_t* out) {
+    if (n < 0 || (n > 0 && (!rows || !out))) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+    const size_t total = (size_t)n * LCM_SIFT_BYTES;
+    for (size_t i = 0; i < total; ++i) {
+        const float v = rows[i];
+        if (!(v >= 0.0f && v <= 255.0f) || v != std::floor(v))
+            return fail(LCM_ERR_INVALID_ARG, "element %zu of row %zu is not an integer in [0, 255]: these are not OpenCV SIFT descriptors",
+                        i % LCM_SIFT_BYTES, i / LCM_SIFT_BYTES);
+    }
+    for (size_t i = 0; i < total; ++i) out[i] = (uint8_t)rows[i];
+    return LCM_OK;
+}
+int lcm_knn2_pair_l2(lcm_handle* h, const uint8_t* query, int nq, const uint8_t* train, int nt, int32_t* train_idx, float* dist,
+                     uint32_t* dist_sq, int* n_neighbours) {
+    return guarded([&] { return knn2_pair_l2_impl(h, query, nq, train, nt, train_idx, dist, dist_sq, n_neighbours); });
+}
+int lcm_match_features_ratio_l2(lcm_handle* h, const uint8_t* query, int nq, const uint8_t* train, int nt, double ratio,
+                                lcm_dmatch* out, int* n_out) {
+    return guarded([&] { return match_features_ratio_l2_impl(h, query, nq, train, nt, ratio, out, n_out); });
+}
+int lcm_match_pairs_ratio_l2(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_frames, const lcm_pair_ref* pairs,
+                             int n_pairs, double ratio, lcm_dmatch* out, size_t cap, size_t* offsets) {
+    return guarded([&] { return match_pairs_ratio_l2_impl(h, frames, rows, n_frames, pairs, n_pairs, ratio, out, cap, offsets); });
+}
+
+}  // extern "C"
