@@ -222,7 +222,11 @@ LCM_API int  lcm_match_stored(lcm_handle* h, int query_frame_id, int train_frame
 /* The same for MANY pairs in ONE launch (the match lists of all loop candidates of a frame): every pair is cut into
  * (query chunk x train segment) work items of one kernel launch, a second kernel folds the segments, one download.
  * out (host) receives the DMatch lists back to back; offsets[n_pairs + 1] (host, required) their bounds; min_dists
- * (host, optional) each pair's minimum distance, -1 if it has no matches.  A pair with an empty side has no matches. */
+ * (host, optional) each pair's minimum distance, -1 if it has no matches.  A pair with an empty side has no matches.
+ * The number of pairs in one call (here and in lcm_match_query_batch, lcm_match_stored_batch_ratio and
+ * lcm_match_query_batch_ratio) is bounded by `int` and by memory, not by a launch grid: the fold kernel goes out in
+ * slices of hipDeviceProp_t::maxGridSize[1] pairs (65535 on the MI355X), so an all-pairs search over a few hundred
+ * frames fits one call. */
 typedef struct lcm_pair_ref { int32_t query_frame_id, train_frame_id; } lcm_pair_ref;
 LCM_API int  lcm_match_stored_batch(lcm_handle* h, const lcm_pair_ref* pairs, int n_pairs,
                                     lcm_dmatch* out, size_t cap, size_t* offsets, int32_t* min_dists);
@@ -288,7 +292,10 @@ LCM_API int  lcm_match_features_ratio_l2(lcm_handle* h, const uint8_t* query, in
  * each uploaded ONCE; pairs[p] = {query position, train position} into `frames` (a position outside [0, n_frames) is
  * LCM_ERR_INVALID_ARG; a pair may name the same matrix on both sides; a pair with an empty side has an empty list).  One
  * score launch plus one fold for the whole set.  The lists come back to back in `out`, bounded by offsets[n_pairs + 1]
- * (required); the match count the reference thresholds at 300 (:1388) is offsets[p+1] - offsets[p]. */
+ * (required); the match count the reference thresholds at 300 (:1388) is offsets[p+1] - offsets[p].
+ * Pairs per call: any n_pairs whose work fits 2^31 - 1 (query chunk x 512-row train segment) items and 2^31 - 1 query
+ * rows in total, LCM_ERR_CAPACITY above that, before anything is launched; the fold over the pairs goes out in slices of
+ * hipDeviceProp_t::maxGridSize[1] pairs, so 65535 pairs (an all-pairs search over 363 frames) is no limit. */
 LCM_API int  lcm_match_pairs_ratio_l2(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_frames,
                                       const lcm_pair_ref* pairs, int n_pairs, double ratio,
                                       lcm_dmatch* out, size_t cap, size_t* offsets);

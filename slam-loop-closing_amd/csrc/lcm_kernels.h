@@ -123,7 +123,12 @@ struct FoldArgs {
     const PairDesc* pairs;
     uint32_t*       final_keys;
     uint32_t        n_pairs;
+    uint32_t        pair_base;   // set by the launchers: pair of blockIdx.y == 0 (a call's pairs go out in slices, below)
 };
+// gridDim.y carries the pairs of a fold launch.  Its limit is the current device's hipDeviceProp_t::maxGridSize[1] (read
+// once per device and kept): the fold launchers cut a call's pairs into slices of at most that many, one launch each, so
+// that the number of pairs in a call is bounded by its buffers alone.
+hipError_t grid_y_limit(uint32_t* limit);
 hipError_t launch_fold_pair_keys(const FoldArgs& a, uint32_t max_nq, hipStream_t st);
 // bytes (rounded up to 16; both buffers must have that room, 16-byte aligned) from PINNED host memory to device memory, by
 // a kernel on `st` instead of a DMA-engine copy (latency-critical small uploads)
@@ -195,6 +200,8 @@ struct L2FoldArgs {
     uint2*          flagged;
     uint32_t        flag_cap;
     const uint8_t*  raw;
+    uint32_t        job_base;    // set by launch_l2_fold: job of blockIdx.y == 0 (slices of grid_y_limit() jobs); `flagged` holds
+                                 // the job's index in `jobs`, whatever the slice
 };
 hipError_t launch_l2_fold(const L2FoldArgs& a, uint32_t n_jobs, uint32_t max_nq, hipStream_t st);
 hipError_t launch_l2_rescan(const L2FoldArgs& a, hipStream_t st);

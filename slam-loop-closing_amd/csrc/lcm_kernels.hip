@@ -27,6 +27,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <atomic>
+
 #include "lcm_kernels.h"
 
 #ifndef LCM_INNER_PRIO
@@ -776,7 +779,7 @@ __global__ __launch_bounds__(256) void k_finalize_pairs(FinalizeArgs a, uint32_t
 // of a single matchFeatures call's fold time), the 8 partial minima meet in LDS.
 __global__ __launch_bounds__(256) void k_fold_pair_keys(FoldArgs a) {
     __shared__ uint32_t part_min[8][32];
-    const PairDesc p = a.pairs[blockIdx.y];
+    const PairDesc p = a.pairs[a.pair_base + blockIdx.y];
     const uint32_t rr = threadIdx.x & 31u, part = threadIdx.x >> 5;
     const uint32_t r = blockIdx.x * 32u + rr;
     const uint32_t CR = a.chunk_rows ? a.chunk_rows : (uint32_t)MAX_FUSED_QUERY_ROWS;
@@ -795,10 +798,38 @@ __global__ __launch_bounds__(256) void k_fold_pair_keys(FoldArgs a) {
     }
 }
 
+hipError_t grid_y_limit(uint32_t* limit) {
+    constexpr int MAX_DEV = 64;
+    static std::atomic<uint32_t> known[MAX_DEV];               // 0 = not read yet
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    uint32_t v = dev >= 0 && dev < MAX_DEV ? known[dev].load(std::memory_order_relaxed) : 0u;
+    if (v == 0) {
+        hipDeviceProp_t prop;
+        e = hipGetDeviceProperties(&prop, dev);
+        if (e != hipSuccess) return e;
+        if (prop.maxGridSize[1] < 1) return hipErrorInvalidValue;
+        v = (uint32_t)prop.maxGridSize[1];
+        if (dev >= 0 && dev < MAX_DEV) known[dev].store(v, std::memory_order_relaxed);
+    }
+    *limit = v;
+    return hipSuccess;
+}
+
 hipError_t launch_fold_pair_keys(const FoldArgs& a, uint32_t max_nq, hipStream_t st) {
     if (a.n_pairs == 0 || max_nq == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_fold_pair_keys, dim3((max_nq + 31) / 32, a.n_pairs), dim3(256), 0, st, a);
-    return hipGetLastError();
+    uint32_t lim = 0;
+    hipError_t e = grid_y_limit(&lim);
+    if (e != hipSuccess) return e;
+    FoldArgs s = a;
+    for (s.pair_base = 0; s.pair_base < a.n_pairs; s.pair_base += lim) {
+        hipLaunchKernelGGL(k_fold_pair_keys, dim3((max_nq + 31) / 32, std::min(lim, a.n_pairs - s.pair_base)), dim3(256), 0, st, s);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        if (a.n_pairs - s.pair_base <= lim) break;             // pair_base + lim may not fit 32 bits
+    }
+    return hipSuccess;
 }
 
 // Upload by kernel: n16 16-byte words from pinned host memory (mapped into the device's address space) to device memory.

@@ -20,6 +20,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "lcm_kernels.h"
 
 namespace lcm {
@@ -161,7 +163,7 @@ __device__ __forceinline__ void top2_insert(uint32_t& b1, uint32_t& b2, uint32_t
 // partial lists meet in LDS.  Keys of different segments never compare equal, so the merge is exact.
 __global__ __launch_bounds__(256) void k_fold_pair_keys2(FoldArgs a) {
     __shared__ uint2 part_top[8][32];
-    const PairDesc p = a.pairs[blockIdx.y];
+    const PairDesc p = a.pairs[a.pair_base + blockIdx.y];
     const uint32_t rr = threadIdx.x & 31u, part = threadIdx.x >> 5;
     const uint32_t r = blockIdx.x * 32u + rr;
     const uint32_t CR = a.chunk_rows ? a.chunk_rows : (uint32_t)MAX_FUSED_QUERY_ROWS;
@@ -191,8 +193,17 @@ __global__ __launch_bounds__(256) void k_fold_pair_keys2(FoldArgs a) {
 
 hipError_t launch_fold_pair_keys2(const FoldArgs& a, uint32_t max_nq, hipStream_t st) {
     if (a.n_pairs == 0 || max_nq == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_fold_pair_keys2, dim3((max_nq + 31) / 32, a.n_pairs), dim3(256), 0, st, a);
-    return hipGetLastError();
+    uint32_t lim = 0;
+    hipError_t e = grid_y_limit(&lim);
+    if (e != hipSuccess) return e;
+    FoldArgs s = a;                                            // slices of at most gridDim.y's limit, as launch_fold_pair_keys
+    for (s.pair_base = 0; s.pair_base < a.n_pairs; s.pair_base += lim) {
+        hipLaunchKernelGGL(k_fold_pair_keys2, dim3((max_nq + 31) / 32, std::min(lim, a.n_pairs - s.pair_base)), dim3(256), 0, st, s);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        if (a.n_pairs - s.pair_base <= lim) break;
+    }
+    return hipSuccess;
 }
 
 }  // namespace lcm

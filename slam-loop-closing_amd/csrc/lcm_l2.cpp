@@ -122,7 +122,7 @@ int l2_run(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_f
     h->info.workgroups = (uint32_t)n_items; h->info.route = LCM_ROUTE_PLAIN; h->info.launches = 4;
     h->info.pairs = P; h->info.distances = distances; h->info.algo_bytes = 2 * n_tiles * (uint64_t)lcm::L2_TILE_BYTES + total_rows * 16;
     const lcm::L2FoldArgs fa{s.d_seg, (uint32_t)CH, reinterpret_cast<const lcm::L2Job*>(s.d_tab + off_jobs), s.d_fin,
-                             reinterpret_cast<uint32_t*>(s.d_tab + off_counter), s.d_flag, (uint32_t)total_rows, s.d_raw};
+                             reinterpret_cast<uint32_t*>(s.d_tab + off_counter), s.d_flag, (uint32_t)total_rows, s.d_raw, 0};
     e = lcm::launch_l2_fold(fa, (uint32_t)P, (uint32_t)max_nq, h->stream);
     if (e != hipSuccess) return fail(LCM_ERR_HIP, "fold kernel launch failed: %s", hipGetErrorString(e));
     e = lcm::launch_l2_rescan(fa, h->stream);

@@ -47,6 +47,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "lcm_kernels.h"
 
 namespace lcm {
@@ -210,7 +212,8 @@ hipError_t launch_l2_score(const L2ScoreArgs& a, uint32_t n_items, hipStream_t s
 
 // ---- fold over segments ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_l2_fold(L2FoldArgs a) {
-    const L2Job jb = a.jobs[blockIdx.y];
+    const uint32_t job = a.job_base + blockIdx.y;
+    const L2Job jb = a.jobs[job];
     const uint32_t r = blockIdx.x * 256u + threadIdx.x;
     if (r >= jb.nq) return;
     const uint32_t c = r / a.chunk_rows, lr = r % a.chunk_rows;
@@ -232,14 +235,23 @@ __global__ __launch_bounds__(256) void k_l2_fold(L2FoldArgs a) {
     a.final_keys[(size_t)jb.out_row0 + r] = make_uint4(d1, i1, d2, i2);
     if (d2 != L2_NONE && d2 >= L2_RESCAN_MIN) {
         const uint32_t slot = atomicAdd(a.counter, 1u);
-        if (slot < a.flag_cap) a.flagged[slot] = make_uint2(blockIdx.y, r);
+        if (slot < a.flag_cap) a.flagged[slot] = make_uint2(job, r);
     }
 }
 
 hipError_t launch_l2_fold(const L2FoldArgs& a, uint32_t n_jobs, uint32_t max_nq, hipStream_t st) {
     if (n_jobs == 0 || max_nq == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_l2_fold, dim3((max_nq + 255) / 256, n_jobs), dim3(256), 0, st, a);
-    return hipGetLastError();
+    uint32_t lim = 0;
+    hipError_t e = grid_y_limit(&lim);
+    if (e != hipSuccess) return e;
+    L2FoldArgs s = a;                                          // slices of at most gridDim.y's limit (lcm_kernels.h)
+    for (s.job_base = 0; s.job_base < n_jobs; s.job_base += lim) {
+        hipLaunchKernelGGL(k_l2_fold, dim3((max_nq + 255) / 256, std::min(lim, n_jobs - s.job_base)), dim3(256), 0, st, s);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        if (n_jobs - s.job_base <= lim) break;
+    }
+    return hipSuccess;
 }
 
 // ---- rescan of the rows whose second neighbour may share a float root with its rival ----------------------------------
