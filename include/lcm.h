@@ -31,6 +31,9 @@
  *   lcm_loop_candidate    <- struct LoopCandidate (include/loop_closing.hpp:22-27), same field order
  *   lcm_knn2_pair_l2, lcm_match_features_ratio_l2, lcm_match_pairs_ratio_l2 <- the same matcher on what the reference
  *                            feeds it: 128-D cv::SIFT rows under cv::NORM_L2 (src/main.cpp:497-504, :517)
+ *   lcm_score_pairs_ratio_l2 <- what the loop search keeps of that call: matches.size() per pair (src/main.cpp:1386-1388),
+ *                            counted on the device; lcm_loop_search_ratio_l2 is the whole loop (:1375-1388) on SIFT rows;
+ *                            lcm_l2_ratio_test_device exposes the device's ratio-test verdict to tests
  *   lcm_dmatch            <- cv::DMatch as consumed at src/main.cpp:551-555 (queryIdx, trainIdx, imgIdx, distance)
  *
  * Conventions
@@ -299,6 +302,49 @@ LCM_API int  lcm_match_features_ratio_l2(lcm_handle* h, const uint8_t* query, in
 LCM_API int  lcm_match_pairs_ratio_l2(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_frames,
                                       const lcm_pair_ref* pairs, int n_pairs, double ratio,
                                       lcm_dmatch* out, size_t cap, size_t* offsets);
+
+/* ---- loop search on SIFT rows: ratio-test COUNTS per pair, decided on the device ------------------------------------ */
+/* The reference's loop search (src/main.cpp:1375-1388) runs matchFeatures(desc[curr], desc[past], matches, 0.7) on every
+ * admissible keyframe pair and looks at matches.size() only.  The count depends on each query row's two smallest float
+ * distances alone — the roots of its two smallest D, as a multiset — so no index, no per-row list and no match record is
+ * formed: one workgroup per chunk of 128 or 256 query rows walks the pair's whole train matrix (k_l2_count, route
+ * LCM_ROUTE_PLAIN), takes the exact float roots ((float)sqrt((double)D) has sqrtf's bits for every D <= 8 323 200) and the
+ * IEEE double comparison on the device, and 8 bytes per pair come back.  For every pair good_count equals
+ * offsets[p+1] - offsets[p] of lcm_match_pairs_ratio_l2, and min_dist_sq is the pair's smallest D (the smallest dist_sq that
+ * lcm_knn2_pair_l2 reports, unless three train rows tie at the float root of a row's minimum).
+ * A call with few pairs does not fill the chip (a pair is at most 512 workgroups of 128 rows, 32 at 4000 rows): the single
+ * pair's call remains lcm_match_features_ratio_l2.  LCM_TUNE_L2_COUNT_CHUNK = 128 | 256 (environment) pins the chunk;
+ * lcm_last_launch_info: workgroups = sum over the pairs with two non-empty sides of ceil(query rows / chunk), kernel_ms
+ * around the count kernel. */
+typedef struct lcm_l2_score {      /* 8 bytes, one per pair */
+    uint32_t good_count;           /* query rows with (double)s1 < ratio * (double)s2; rows with < 2 neighbours do not count */
+    uint32_t min_dist_sq;          /* min over query rows of D1; 0xFFFFFFFF if either side is empty */
+} lcm_l2_score;
+/* Arguments and refusals of lcm_match_pairs_ratio_l2 (cross_check, ratio, row counts, positions, NULLs; LCM_ERR_CAPACITY
+ * above 2^31 - 1 items); a pair may name one matrix on both sides; a pair with an empty side yields {0, 0xFFFFFFFF} and
+ * launches nothing.  Ordered on the handle's stream, finished on return; the records are re-initialised on the stream
+ * by every call. */
+LCM_API int  lcm_score_pairs_ratio_l2(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_frames,
+                                      const lcm_pair_ref* pairs, int n_pairs, double ratio, lcm_l2_score* scores);
+/* The loop at src/main.cpp:1375-1388 in one call, on POSITIONS into `frames`: curr in [loop_gap, n_frames), past in
+ * [0, curr - loop_gap], in that order; a pair is skipped, before scoring, if skip[curr] or skip[past] is non-zero
+ * (`poses[i].R.empty()`, :1377 / :1381; skip == NULL: none) or either matrix has fewer than rp->min_rows rows (:1382).
+ * *n_pairs_out (optional) = pairs scored.  A pair is a candidate iff good_count >= rp->min_matches (:1388):
+ * current_frame_id = curr, matched_frame_id = past, num_matches = good_count, similarity_score = (double)good_count /
+ * (double)min(rows) in IEEE double (0.0 for an empty side) — informational.  Candidates come in (curr, past) order; the
+ * verdict runs on the host over the 8-byte records.  rp == NULL: ratio 0.7, min_rows 100, min_matches 300
+ * (lcm_ratio_loop_params, below).  loop_gap < 1 is LCM_ERR_INVALID_ARG (the reference's max(3, numViews / 2) stays with
+ * the caller); more candidates than `cap` (or out == NULL with candidates present) is LCM_ERR_CAPACITY: *n_out is then the
+ * count and nothing is written to `out`. */
+struct lcm_ratio_loop_params;
+LCM_API int  lcm_loop_search_ratio_l2(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_frames,
+                                      const uint8_t* skip, int loop_gap, const struct lcm_ratio_loop_params* rp,
+                                      lcm_loop_candidate* out, size_t cap, size_t* n_out, size_t* n_pairs_out);
+/* Diagnostic: pass[i] (0 or 1) = the verdict of the count kernel's own device function on the squared distances
+ * (d1[i], d2[i]) of a first and a second neighbour, n host-given pairs; a value above 8 323 200 is LCM_ERR_INVALID_ARG.
+ * Descriptor inputs can only sample the range of D: this lets a test walk all of it. */
+LCM_API int  lcm_l2_ratio_test_device(lcm_handle* h, const uint32_t* d1, const uint32_t* d2, size_t n, double ratio,
+                                      uint8_t* pass);
 
 /* ---- loop search against the stored database --------------------------------------------------------- */
 /* Score `query` (id query_frame_id) against every stored frame with query_frame_id - id >= min_gap, ascending

@@ -82,7 +82,9 @@ SCORE_DTYPE = np.dtype([("good_count", "<u4"), ("min_dist", "<u2"), ("n_train", 
 DMATCH_DTYPE = np.dtype([("query_idx", "<i4"), ("train_idx", "<i4"), ("img_idx", "<i4"), ("distance", "<f4")])
 CANDIDATE_DTYPE = np.dtype([("current_frame_id", "<i4"), ("matched_frame_id", "<i4"), ("num_matches", "<i4"),
                             ("_pad", "<i4"), ("similarity_score", "<f8")])
+L2_SCORE_DTYPE = np.dtype([("good_count", "<u4"), ("min_dist_sq", "<u4")])      # lcm_l2_score
 assert SCORE_DTYPE.itemsize == C.sizeof(Score) == 8
+assert L2_SCORE_DTYPE.itemsize == 8
 assert DMATCH_DTYPE.itemsize == C.sizeof(DMatch) == 16
 assert CANDIDATE_DTYPE.itemsize == C.sizeof(LoopCandidate) == 24
 
@@ -127,6 +129,10 @@ _SIGNATURES = {
     "lcm_knn2_pair_l2": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _i32p]),
     "lcm_match_features_ratio_l2": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_double, _vp, _i32p]),
     "lcm_match_pairs_ratio_l2": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_double, _vp, C.c_size_t, _vp]),
+    "lcm_score_pairs_ratio_l2": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_double, _vp]),
+    "lcm_loop_search_ratio_l2": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(RatioLoopParams), _vp, C.c_size_t,
+                                            C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "lcm_l2_ratio_test_device": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_double, _vp]),
     "lcm_query_scores": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _i32p]),
     "lcm_query_submit": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _i32p]),
     "lcm_query_collect": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i32p]),
@@ -532,6 +538,56 @@ class Matcher:
         _check(self._lib.lcm_match_pairs_ratio_l2(self._h, C.cast(ptrs, _vp), rows.ctypes.data_as(_vp), len(fr), _ptr(pr), n,
                                                   ratio, out.ctypes.data_as(_vp), cap, offs.ctypes.data_as(_vp)))
         return [out[int(offs[i]): int(offs[i + 1])] for i in range(n)], offs
+
+    # -- loop search on SIFT rows: ratio-test counts per pair, decided on the device -----------------
+    @staticmethod
+    def _sift_frames(frames):
+        fr = [_sift_rows(f) for f in frames]
+        ptrs = (_vp * max(len(fr), 1))(*[f.ctypes.data if f.size else None for f in fr])
+        rows = np.array([f.shape[0] for f in fr] or [0], np.int32)
+        return fr, ptrs, rows
+
+    def score_pairs_ratio_l2(self, frames: Sequence[np.ndarray], pairs: Sequence[Tuple[int, int]], ratio: float) -> np.ndarray:
+        """Per (query position, train position) pair into `frames` (SIFT matrices, each uploaded once): the number of query
+        rows that pass Lowe's ratio test and the smallest squared distance, L2_SCORE_DTYPE[n]; nothing else leaves the
+        device."""
+        fr, ptrs, rows = self._sift_frames(frames)
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n = pr.shape[0]
+        out = np.zeros(max(n, 1), L2_SCORE_DTYPE)
+        _check(self._lib.lcm_score_pairs_ratio_l2(self._h, C.cast(ptrs, _vp), rows.ctypes.data_as(_vp), len(fr), _ptr(pr), n,
+                                                  ratio, out.ctypes.data_as(_vp)))
+        return out[:n]
+
+    def loop_search_ratio_l2(self, frames: Sequence[np.ndarray], loop_gap: int, skip=None, ratio: Optional[float] = None,
+                             min_rows: Optional[int] = None, min_matches: Optional[int] = None, cap: Optional[int] = None,
+                             out: Optional[np.ndarray] = None) -> Tuple[np.ndarray, int]:
+        """The reference's loop search (src/main.cpp:1375-1388) over SIFT matrices by position: (candidates in (curr, past)
+        order, pairs scored).  skip: optional flags, one per frame.  ratio / min_rows / min_matches left at None: 0.7 / 100
+        / 300 (all three None: rp = NULL)."""
+        fr, ptrs, rows = self._sift_frames(frames)
+        rp = _ratio_loop_params(ratio, min_rows, min_matches)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+        assert sk is None or sk.shape == (len(fr),)
+        if out is None:
+            cap = len(fr) * len(fr) if cap is None else cap
+            out = np.zeros(max(cap, 1), CANDIDATE_DTYPE)
+        else:
+            assert out.dtype == CANDIDATE_DTYPE and out.flags["C_CONTIGUOUS"]
+            cap = len(out) if cap is None else cap
+        n, npairs = C.c_size_t(0), C.c_size_t(0)
+        _check(self._lib.lcm_loop_search_ratio_l2(self._h, C.cast(ptrs, _vp), rows.ctypes.data_as(_vp), len(fr), _ptr(sk),
+                                                  loop_gap, None if rp is None else C.byref(rp), out.ctypes.data_as(_vp), cap,
+                                                  C.byref(n), C.byref(npairs)))
+        return out[: n.value], npairs.value
+
+    def l2_ratio_test_device(self, d1, d2, ratio: float) -> np.ndarray:
+        """Diagnostic: the count kernel's ratio-test verdict on squared distances (d1[i], d2[i]) -> uint8[n] of 0 / 1."""
+        a, b = np.ascontiguousarray(d1, np.uint32).ravel(), np.ascontiguousarray(d2, np.uint32).ravel()
+        assert a.shape == b.shape
+        out = np.full(max(a.size, 1), 0xFF, np.uint8)
+        _check(self._lib.lcm_l2_ratio_test_device(self._h, _ptr(a), _ptr(b), a.size, ratio, out.ctypes.data_as(_vp)))
+        return out[: a.size]
 
     # -- loop search -------------------------------------------------------------------------------
     def query_scores(self, query, query_frame_id: int) -> Tuple[np.ndarray, np.ndarray]:

@@ -223,6 +223,8 @@ void lcm_destroy(lcm_handle* h) {
     (void)hipFree(h->l2.d_raw); (void)hipFree(h->l2.d_img); (void)hipFree(h->l2.d_tw); (void)hipFree(h->l2.d_tab);
     (void)hipFree(h->l2.d_seg); (void)hipFree(h->l2.d_fin); (void)hipFree(h->l2.d_flag);
     if (h->l2.h_fin) (void)hipHostFree(h->l2.h_fin);
+    (void)hipFree(h->l2.d_score); (void)hipFree(h->l2.d_diag);
+    if (h->l2.h_score) (void)hipHostFree(h->l2.h_score);
     for (QuerySlot& q : h->qslots) {
         (void)hipFree(q.d_query); (void)hipFree(q.d_scores); (void)hipFree(q.d_dist); (void)hipFree(q.d_meta);
         if (q.h_meta) (void)hipHostFree(q.h_meta);

@@ -5,7 +5,7 @@
 //   lcm_mfma_host.cpp  opt-in matrix-core variants    lcm_group.cpp    multi-GPU group (RCCL)
 //   lcm_knn.cpp        pair mode with k = 2 neighbours + Lowe's ratio test
 //   lcm_ratio.cpp      bulk / online loop search scored with Lowe's ratio test
-//   lcm_l2.cpp         pair mode on 128-byte SIFT rows under L2 (knnMatch(k = 2) + ratio test)
+//   lcm_l2.cpp         pair mode on 128-byte SIFT rows under L2 (knnMatch(k = 2) + ratio test), ratio-test counts per pair
 // Not installed; the public surface is include/lcm.h.
 #pragma once
 #include "../../include/lcm.h"
@@ -234,6 +234,11 @@ struct lcm_handle {
         uint4* d_fin = nullptr;    size_t d_fin_n = 0;
         uint2* d_flag = nullptr;   size_t d_flag_n = 0;
         uint4* h_fin = nullptr;    size_t h_fin_n = 0;
+        // ... and of the count calls (lcm_score_pairs_ratio_l2): one record per live pair, device + pinned landing zone;
+        // the diagnostic's [d1 | d2 | pass]
+        uint2* d_score = nullptr;  size_t d_score_n = 0;
+        lcm_l2_score* h_score = nullptr; size_t h_score_n = 0;
+        uint32_t* d_diag = nullptr; size_t d_diag_n = 0;
     } l2;
     lcm_launch_info info{};
     bool info_pending = false;

@@ -206,6 +206,25 @@ struct L2FoldArgs {
 hipError_t launch_l2_fold(const L2FoldArgs& a, uint32_t n_jobs, uint32_t max_nq, hipStream_t st);
 hipError_t launch_l2_rescan(const L2FoldArgs& a, hipStream_t st);
 
+// ---- ratio-test counts per pair on SIFT rows (lcm_l2_count.hip): the loop search's score, src/main.cpp:1375-1388 --------
+// One workgroup = one item: q_rows <= chunk_rows query rows starting at tile q_tile against the WHOLE train matrix of
+// pair `pair` (t_rows rows starting at tile t_tile).  Per pair one 8-byte record (include/lcm.h, lcm_l2_score): the kernel
+// adds each wave's survivors to good_count and takes the minimum of its rows' D1 into min_dist_sq.
+constexpr uint32_t L2_MAX_DSQ = 128u * 255u * 255u;    // 8 323 200
+struct L2CountItem { uint32_t q_tile, q_rows, t_tile, t_rows, pair, reserved[3]; };
+struct L2CountArgs {
+    const uint8_t*     img;
+    const uint32_t*    tw;
+    const L2CountItem* items;
+    uint2*             scores;      // (good_count, min_dist_sq) per pair, initialised by launch_l2_count_init
+    double             ratio;
+    uint32_t           chunk_rows;  // 128 (one query tile per wave) or 256 (two)
+};
+hipError_t launch_l2_count_init(uint2* scores, uint32_t n_pairs, hipStream_t st);      // every record <- (0, 0xFFFFFFFF)
+hipError_t launch_l2_count(const L2CountArgs& a, uint32_t n_items, hipStream_t st);
+// pass[i] = the count kernel's verdict on (d1[i], d2[i]), both <= L2_MAX_DSQ: one thread each, grid-stride
+hipError_t launch_l2_ratio_test(const uint32_t* d1, const uint32_t* d2, size_t n, double ratio, uint8_t* pass, hipStream_t st);
+
 // ---- bulk / online loop search scored with Lowe's ratio test (lcm_ratio.hip): src/main.cpp:1375-1388 -------------------
 // One workgroup = one WorkItem (or an implicit run of stored slots for ONE query frame, as ScoreArgs' implicit items):
 // per pair, good_count = number of query rows with best < ratio * second (knnMatch(k = 2) order, the second smallest

@@ -50,13 +50,9 @@
 #include <algorithm>
 
 #include "lcm_kernels.h"
+#include "lcm_l2_device.h"
 
 namespace lcm {
-
-typedef int l2_v4i __attribute__((ext_vector_type(4)));
-typedef int l2_v16i __attribute__((ext_vector_type(16)));
-
-constexpr uint32_t L2_NONE = 0xFFFFFFFFu;      // "no neighbour": above every real key (at most 8323200 << 9 | 511)
 
 // ---- raw rows -> operand image + per-row word ------------------------------------------------------------------------
 __device__ __forceinline__ int l2_sq4(uint32_t w) {           // sum of squares of the four int8 of w
@@ -96,43 +92,7 @@ hipError_t launch_l2_pack(const L2PackArgs& a, hipStream_t st) {
 }
 
 // ---- the score kernel ------------------------------------------------------------------------------------------------
-// (b1, b2) <- the two smallest of {b1, b2, k0, k1}, b1 <= b2: lcm_knn.hip's update
-__device__ __forceinline__ void l2_top2_pair(uint32_t& b1, uint32_t& b2, uint32_t k0, uint32_t k1) {
-    uint32_t m;
-    asm("v_med3_u32 %0, %1, %2, %3" : "=v"(m) : "v"(b1), "v"(k0), "v"(k1));
-    b2 = min(b2, m);
-    b1 = min(min(b1, k0), k1);
-}
-
-__device__ __forceinline__ void l2_top2_insert(uint32_t& b1, uint32_t& b2, uint32_t k) {
-    b2 = min(b2, max(b1, k));
-    b1 = min(b1, k);
-}
-
-// 16 accumulators of one lane -> 16 keys -> the lane's running top-2.  tw[reg] = the train row's word, qterm = the query
-// row's |q'|^2 << 9; |dot| <= 2^21 fits the 24-bit multiply.  CHECK: rows >= nt of the tile (row0 = first row of this
-// lane's half: 32 t + 4 h) get L2_NONE.
-template <bool CHECK>
-__device__ __forceinline__ void l2_epilogue(const l2_v16i& acc, const uint32_t (&tw)[16], uint32_t qterm, uint32_t& b1, uint32_t& b2,
-                                            uint32_t row0, uint32_t nt) {
-    uint32_t key[16];
-    int m1024;
-    asm("s_movk_i32 %0, 0xfc00" : "=s"(m1024));                  // -1024
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-        // key = (tw + qterm) - (dot << 10) as one v_mad_i32_i24: m1024 is opaque to the compiler, which would otherwise
-        // shift and subtract.  The accumulators are read by compiler-visible code only (never by inline asm): the wait
-        // states between an MFMA and the VALU that reads its result are inserted by the compiler.
-        key[reg] = (uint32_t)(__mul24(acc[reg], m1024) + (int)(tw[reg] + qterm));
-        if (CHECK) {
-            const uint32_t row = row0 + (uint32_t)((reg & 3) + 8 * (reg >> 2));
-            key[reg] = row < nt ? key[reg] : L2_NONE;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 16; i += 2) l2_top2_pair(b1, b2, key[i], key[i + 1]);
-}
-
+// the exact top-2 update and the key epilogue: lcm_l2_device.h (shared with lcm_l2_count.hip)
 template <int QT>
 __global__ __launch_bounds__(256, QT == 1 ? 4 : 3) void k_l2_score(L2ScoreArgs a) {
     const L2Item it = a.items[blockIdx.x];
