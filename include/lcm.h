@@ -245,7 +245,11 @@ LCM_API int  lcm_match_query_batch(lcm_handle* h, const uint8_t* query, int nq, 
  * consecutive frames (src/main.cpp:1154) and 0.7 for the loop search (:1386).  These calls do not consult
  * lcm_params.ratio / dist_floor; they return LCM_ERR_INVALID_ARG while cross_check != 0 (OpenCV asserts knn == 1 under
  * crossCheck) and for a ratio that is NaN or negative.  Errors, capacities, empty sides and `offsets` are those of the
- * k = 1 calls above; records have img_idx = 0 and the integer-valued distance of `best`. */
+ * k = 1 calls above; records have img_idx = 0 and the integer-valued distance of `best`.
+ * Sizes (tests/test_gpu_knn_limits.py runs each at its limit): a train matrix of lcm_knn2_pair / lcm_match_features_ratio
+ * holds up to LCM_MAX_TRAIN_ROWS rows (LCM_ERR_CAPACITY above; both neighbours' indices use the key's 22 bits), nq is
+ * not limited there; stored frames take part with up to 65535 rows on either side; the host query of
+ * lcm_match_query_batch_ratio may hold up to 131072 rows (64 x 2048; LCM_ERR_CAPACITY above), as lcm_match_query_batch's. */
 /* knnMatch(k=2) (src/main.cpp:520): train_idx[2*q + k], dist[2*q + k], k = 0 best, 1 second; a missing second neighbour
  * (nt == 1) is train_idx = -1, dist = 0xFFFF.  *n_neighbours = min(nt, 2), 0 if either side is empty (nothing written then). */
 LCM_API int  lcm_knn2_pair(lcm_handle* h, const uint8_t* query, int nq, const uint8_t* train, int nt,
@@ -411,7 +415,9 @@ LCM_API int  lcm_all_vs_all_loops(lcm_handle* h, const void* d_query_rows, const
  * query row's two smallest distances and counts on the device (route LCM_ROUTE_PLAIN).  The reference's `rows < 100`
  * skip and its `>= 300` threshold stay with the caller, on the records and the frames' row counts.
  * LCM_ERR_INVALID_ARG while cross_check != 0 and for a NaN or negative ratio, as the k = 2 pair calls; LCM_ERR_CAPACITY
- * for a query frame above 2048 rows (there is no packed route here) and for a too-small scores_cap (nothing written). */
+ * for a query frame above 2048 rows (there is no packed route here; a stored frame that is no query frame of the call —
+ * no eligible partner — may be taller) and for a too-small scores_cap (nothing written).  Stored frames take part with up
+ * to 65535 rows; n_train uses all 16 bits of its field. */
 LCM_API int  lcm_all_vs_all_ratio(lcm_handle* h, const void* d_query_rows, const int32_t* d_query_counts,
                                   const int32_t* q_ids, int n_q_frames, int q_stride_rows, double ratio,
                                   void* d_scores, size_t scores_cap, size_t* n_pairs, size_t* pair_offsets);

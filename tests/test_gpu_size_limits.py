@@ -8,7 +8,9 @@ Every test owns its handle and frees it in `finally`; nothing is retried."""
 import numpy as np
 import pytest
 
+import knnref
 import limitcases as L
+import ratioref
 
 pytestmark = pytest.mark.gpu
 
@@ -568,6 +570,10 @@ def test_arena_beyond_4_gib(pkg, oracle):
     re-pitch, and 20 seeded others: lcm_db_read, lcm_query_scores, lcm_detect_loops (a planted revisit of the first slot
     above 2^32), lcm_all_vs_all / _argmin with an external 4-frame query set (plain and packed), lcm_match_stored across
     the boundary.  Kernel variants 0 and 1 only (the matrix-core image would be 8 times the arena).
+    Then, on the same arena, the two-neighbour routes against knnref / ratioref: lcm_query_scores_ratio and
+    lcm_detect_loops_ratio on the planted revisit (all 2000 rows pass at 0.7; no other frame reaches 300),
+    lcm_all_vs_all_ratio with the revisit as an external query frame at 4 slots on each side of the boundary (and equal to
+    the online call's records everywhere), lcm_match_stored_ratio for the pair across the boundary in both orders.
     Peak device memory is the two arenas side by side during the re-pitch, 8.0 GiB, later one arena beside the packed
     route's 1 GiB scratch.  The test skips, with the reason printed, only when torch.cuda.mem_get_info() reports less
     than 12 GiB free; nothing else skips it."""
@@ -654,6 +660,35 @@ def test_arena_beyond_4_gib(pkg, oracle):
             om, omin = oracle.match_features(frames[c], frames[i], p)
             np.testing.assert_array_equal(lst, om.astype(lst.dtype), err_msg=f"{c} x {i}")
             assert md == omin
+        # ---- the two-neighbour routes on the same arena (references: knnref / ratioref) ----------------------------------
+        m.set_kernel_variant(0)
+        near = [lo - 3, lo - 2, lo - 1, lo, lo + 1, lo + 2, lo + 3, lo + 4]      # 4 slots on each side of byte offset 2^32
+        for s_ in near:
+            frames.setdefault(s_, _big_frame(s_))
+        at_r = sorted(set(sample) | set(near))
+        want_r = np.zeros(len(at_r), wsc.dtype)
+        for k, s_ in enumerate(at_r):
+            want_r[k] = ratioref.ratio_counts(rev, frames[s_], 0.7) + (BIG_ROWS,)
+        assert int(want_r[at_r.index(lo + 1)]["good_count"]) == BIG_ROWS and int(want_r[at_r.index(lo)]["good_count"]) == 0
+        sc, ids = m.query_scores_ratio(rev, int(q_ids[0]), 0.7)                  # 67140 eligible frames: 4 slots per workgroup
+        assert len(sc) == BIG_N and np.array_equal(ids, np.arange(BIG_N)) and m.launch_info().workgroups == -(-BIG_N // 4)
+        np.testing.assert_array_equal(sc[at_r], want_r)
+        assert int((sc["n_train"] != BIG_ROWS).sum()) == 0 and int((sc["good_count"] >= 300).sum()) == 1
+        cands = m.detect_loops_ratio(int(q_ids[0]), rev, 0.7, 100, 300)
+        assert _tuples(cands) == [(int(q_ids[0]), lo + 1, BIG_ROWS, 1.0)]
+        got[:] = 0
+        assert m.all_vs_all_ratio(0.7, d, n, d_query_rows=dq, d_query_counts=dc, q_ids=q_ids[:1], q_stride_rows=BIG_ROWS) == BIG_N
+        m.sync(); m.dev_download(d, got)
+        np.testing.assert_array_equal(got[near], want_r[[at_r.index(s_) for s_ in near]])
+        np.testing.assert_array_equal(got[:BIG_N], sc)                         # bulk == online, all 67140 records
+        for c, i in ((lo + 1, lo), (lo, lo + 1)):
+            ri, rd = knnref.knn2(frames[c], frames[i])
+            rows_, tidx, dist = knnref.ratio_filter(ri, rd, 1.0)
+            lst = m.match_stored_ratio(c, i, 1.0)
+            assert 0 < len(rows_) < BIG_ROWS and not lst["img_idx"].any()
+            np.testing.assert_array_equal(lst["query_idx"], rows_)
+            np.testing.assert_array_equal(lst["train_idx"], tidx)
+            np.testing.assert_array_equal(lst["distance"], dist)
     finally:
         for b in bufs:
             m.dev_free(b)
