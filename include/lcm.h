@@ -281,7 +281,8 @@ LCM_API int  lcm_match_query_batch_ratio(lcm_handle* h, const uint8_t* query, in
  * Shared with the Hamming k = 2 calls above: LCM_ERR_INVALID_ARG while cross_check != 0, for a NaN or negative ratio, a
  * NULL pointer or a negative count; LCM_ERR_CAPACITY when `cap` is too small, checked before anything is written to `out`;
  * lcm_params.ratio / dist_floor play no part; the work is ordered on the handle's stream and finished on return.  A matrix
- * holds at most 65 535 rows (LCM_ERR_CAPACITY above).  Nothing is stored: the 32-byte database is a different descriptor. */
+ * holds at most 65 535 rows (LCM_ERR_CAPACITY above).  These calls store nothing (the 32-byte database is a different descriptor); the SIFT keyframe
+ * store is lcm_l2_db_*, below. */
 #define LCM_SIFT_BYTES 128
 /* Host only, no device needed: n CV_32F SIFT rows (src/main.cpp:497-504) -> bytes.  LCM_ERR_INVALID_ARG, and nothing
  * written, if any value is not an integer in [0, 255] (NaN, inf, fractions, RootSIFT-normalised rows). */
@@ -349,6 +350,58 @@ LCM_API int  lcm_loop_search_ratio_l2(lcm_handle* h, const uint8_t* const* frame
  * Descriptor inputs can only sample the range of D: this lets a test walk all of it. */
 LCM_API int  lcm_l2_ratio_test_device(lcm_handle* h, const uint32_t* d1, const uint32_t* d2, size_t n, double ratio,
                                       uint8_t* pass);
+
+/* ---- the SIFT keyframe store: rows uploaded and packed ONCE, searched from the device ---------------------------------- */
+/* The calls above take host matrices: each one is uploaded and packed again by every call, and a 32-byte work item per
+ * (pair, query chunk) goes up with them.  The store keeps the matrices on the device — raw rows, operand image and per-row
+ * words, a frame starting at a tile of 32 rows — the way the 32-byte database keeps ORB frames: an online loop check of
+ * one new keyframe (src/main.cpp:1375-1421, one iteration of the outer loop) uploads that keyframe alone, and a search is
+ * launched from tables that grow with the number of FRAMES (at most 32 bytes per scored `curr` and 8 per stored frame):
+ * every workgroup derives its (pair, chunk) item on the device (k_l2_count_store).  The store is separate from the 32-byte
+ * database (lcm_db_*): neither sees the other's frames.  It is not part of lcm_db_save / lcm_db_load or of a group.
+ * A frame is addressed by its SLOT, its position in append order (allDescriptors[i]).  Capacity starts at what the first
+ * append needs and doubles; a growth copies device to device on the handle's stream.  Every call is ordered on the
+ * handle's stream and finished on return, so the caller's rows may be reused at once.
+ * Records, order, refusals and the capacity rule of the store's searches are those of lcm_score_pairs_ratio_l2,
+ * lcm_match_pairs_ratio_l2 and lcm_loop_search_ratio_l2 with the stored matrices as `frames` (cross_check, a NaN or negative
+ * ratio, NULLs, loop_gap < 1, LCM_ERR_CAPACITY above 65 535 rows or 2^31 - 1 items or pairs; *n_out set and `out` untouched
+ * when `cap` is too small); a slot outside [0, lcm_l2_db_size) is LCM_ERR_INVALID_ARG.  LCM_TUNE_L2_COUNT_CHUNK and
+ * lcm_last_launch_info (workgroups, route, pairs, distances, kernel_ms) as for those calls. */
+typedef struct lcm_l2_db_info {        /* 40 bytes */
+    int32_t  frames;                   /* stored frames */
+    int32_t  reserved_;
+    uint64_t tiles_used;               /* tiles of 32 rows taken by the stored frames */
+    uint64_t tiles_reserved;           /* tiles the three arenas have room for */
+    uint64_t device_bytes;             /* device memory of the arenas and the frame table */
+    uint64_t table_bytes;              /* tables uploaded by the last lcm_l2_db_loop_search / lcm_l2_db_detect_loops */
+} lcm_l2_db_info;
+/* Stores n rows (n in [0, 65535]; a frame of 0 rows takes a slot and is never paired); *slot (optional) = its slot. */
+LCM_API int  lcm_l2_db_append(lcm_handle* h, const uint8_t* rows, int n, int* slot);
+LCM_API int  lcm_l2_db_size(lcm_handle* h);                                   /* stored frames; 0 for a NULL handle */
+LCM_API int  lcm_l2_db_rows(lcm_handle* h, int slot, int* n);
+/* The raw rows of a slot back, bit for bit; cap_rows below the frame's rows is LCM_ERR_CAPACITY. */
+LCM_API int  lcm_l2_db_read(lcm_handle* h, int slot, uint8_t* out, int cap_rows);
+/* Keeps the first n_frames slots (their tiles are reused by later appends); clear = truncate to 0.  Memory stays reserved. */
+LCM_API int  lcm_l2_db_truncate(lcm_handle* h, int n_frames);
+LCM_API int  lcm_l2_db_clear(lcm_handle* h);
+LCM_API int  lcm_l2_db_info_read(lcm_handle* h, lcm_l2_db_info* out);
+/* lcm_score_pairs_ratio_l2 / lcm_match_pairs_ratio_l2 with pairs[p] = {query slot, train slot}: nothing is uploaded but
+ * the work tables, nothing is packed. */
+LCM_API int  lcm_l2_db_score_pairs(lcm_handle* h, const lcm_pair_ref* slots, int n_pairs, double ratio, lcm_l2_score* scores);
+LCM_API int  lcm_l2_db_match_pairs_ratio(lcm_handle* h, const lcm_pair_ref* slots, int n_pairs, double ratio,
+                                         lcm_dmatch* out, size_t cap, size_t* offsets);
+/* lcm_loop_search_ratio_l2 over the stored slots (src/main.cpp:1375-1388); skip: one byte per slot, or NULL. */
+LCM_API int  lcm_l2_db_loop_search(lcm_handle* h, const uint8_t* skip, int loop_gap, const struct lcm_ratio_loop_params* rp,
+                                   lcm_loop_candidate* out, size_t cap, size_t* n_out, size_t* n_pairs_out);
+/* One iteration of that search's outer loop: frame `curr` against the slots [0, min(curr - loop_gap, size - 1)], candidates
+ * in ascending slot order with current_frame_id = curr.  query != NULL: the nq host rows stand for position curr (typically
+ * lcm_l2_db_size(h), before the append) and are not stored: they are staged in the arena's free tail, which grows if it
+ * must, and a later append may overwrite them.  query == NULL: curr must be a stored slot (LCM_ERR_INVALID_ARG otherwise)
+ * and its rows are used in place; nq is ignored.  skip (one byte per slot, or NULL) is consulted for the past slots only:
+ * whether `curr` itself is searched is the caller's decision (:1377); rp->min_rows applies to both sides. */
+LCM_API int  lcm_l2_db_detect_loops(lcm_handle* h, int curr, const uint8_t* query, int nq, const uint8_t* skip, int loop_gap,
+                                    const struct lcm_ratio_loop_params* rp, lcm_loop_candidate* out, size_t cap,
+                                    size_t* n_out, size_t* n_pairs_out);
 
 /* ---- loop search against the stored database --------------------------------------------------------- */
 /* Score `query` (id query_frame_id) against every stored frame with query_frame_id - id >= min_gap, ascending

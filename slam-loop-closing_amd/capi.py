@@ -55,6 +55,12 @@ class RatioLoopParams(C.Structure):
     _fields_ = [("ratio", C.c_double), ("min_rows", C.c_int32), ("min_matches", C.c_int32)]
 
 
+class L2DbInfo(C.Structure):
+    """lcm_l2_db_info: the SIFT keyframe store's occupancy and the table bytes of its last search."""
+    _fields_ = [("frames", C.c_int32), ("reserved_", C.c_int32), ("tiles_used", C.c_uint64), ("tiles_reserved", C.c_uint64),
+                ("device_bytes", C.c_uint64), ("table_bytes", C.c_uint64)]
+
+
 class LaunchInfo(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("pairs", C.c_uint64), ("distances", C.c_uint64),
                 ("algo_bytes", C.c_uint64), ("launches", C.c_uint32), ("workgroups", C.c_uint32),
@@ -133,6 +139,19 @@ _SIGNATURES = {
     "lcm_loop_search_ratio_l2": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(RatioLoopParams), _vp, C.c_size_t,
                                             C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "lcm_l2_ratio_test_device": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_double, _vp]),
+    "lcm_l2_db_append": (C.c_int, [_vp, _vp, C.c_int, _i32p]),
+    "lcm_l2_db_size": (C.c_int, [_vp]),
+    "lcm_l2_db_rows": (C.c_int, [_vp, C.c_int, _i32p]),
+    "lcm_l2_db_read": (C.c_int, [_vp, C.c_int, _vp, C.c_int]),
+    "lcm_l2_db_truncate": (C.c_int, [_vp, C.c_int]),
+    "lcm_l2_db_clear": (C.c_int, [_vp]),
+    "lcm_l2_db_info_read": (C.c_int, [_vp, C.POINTER(L2DbInfo)]),
+    "lcm_l2_db_score_pairs": (C.c_int, [_vp, _vp, C.c_int, C.c_double, _vp]),
+    "lcm_l2_db_match_pairs_ratio": (C.c_int, [_vp, _vp, C.c_int, C.c_double, _vp, C.c_size_t, _vp]),
+    "lcm_l2_db_loop_search": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(RatioLoopParams), _vp, C.c_size_t, C.POINTER(C.c_size_t),
+                                         C.POINTER(C.c_size_t)]),
+    "lcm_l2_db_detect_loops": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.POINTER(RatioLoopParams), _vp, C.c_size_t,
+                                          C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "lcm_query_scores": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _i32p]),
     "lcm_query_submit": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _i32p]),
     "lcm_query_collect": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i32p]),
@@ -588,6 +607,97 @@ class Matcher:
         out = np.full(max(a.size, 1), 0xFF, np.uint8)
         _check(self._lib.lcm_l2_ratio_test_device(self._h, _ptr(a), _ptr(b), a.size, ratio, out.ctypes.data_as(_vp)))
         return out[: a.size]
+
+    # -- the SIFT keyframe store: rows uploaded and packed once, searched from the device ----------
+    def l2_db_append(self, rows) -> int:
+        """Stores a SIFT matrix (0..65535 rows); returns its slot."""
+        r = _sift_rows(rows)
+        slot = C.c_int32(-1)
+        _check(self._lib.lcm_l2_db_append(self._h, _ptr(r), r.shape[0], C.byref(slot)))
+        return slot.value
+
+    def l2_db_size(self) -> int:
+        return self._lib.lcm_l2_db_size(self._h)
+
+    def l2_db_rows(self, slot: int) -> int:
+        n = C.c_int32(-1)
+        _check(self._lib.lcm_l2_db_rows(self._h, slot, C.byref(n)))
+        return n.value
+
+    def l2_db_read(self, slot: int) -> np.ndarray:
+        """The raw rows of a slot, uint8[n, 128]."""
+        out = np.zeros((self.l2_db_rows(slot), SIFT_BYTES), np.uint8)
+        _check(self._lib.lcm_l2_db_read(self._h, slot, _ptr(out), out.shape[0]))
+        return out
+
+    def l2_db_truncate(self, n_frames: int):
+        _check(self._lib.lcm_l2_db_truncate(self._h, n_frames))
+
+    def l2_db_clear(self):
+        _check(self._lib.lcm_l2_db_clear(self._h))
+
+    def l2_db_info(self) -> L2DbInfo:
+        info = L2DbInfo()
+        _check(self._lib.lcm_l2_db_info_read(self._h, C.byref(info)))
+        return info
+
+    def l2_db_score_pairs(self, pairs: Sequence[Tuple[int, int]], ratio: float) -> np.ndarray:
+        """score_pairs_ratio_l2 over stored (query slot, train slot) pairs: L2_SCORE_DTYPE[n]."""
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n = pr.shape[0]
+        out = np.zeros(max(n, 1), L2_SCORE_DTYPE)
+        _check(self._lib.lcm_l2_db_score_pairs(self._h, _ptr(pr), n, ratio, out.ctypes.data_as(_vp)))
+        return out[:n]
+
+    def l2_db_match_pairs_ratio(self, pairs: Sequence[Tuple[int, int]], ratio: float, cap: Optional[int] = None):
+        """match_pairs_ratio_l2 over stored (query slot, train slot) pairs: (list of DMatch arrays, offsets[n + 1])."""
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n = pr.shape[0]
+        if cap is None:
+            size = self.l2_db_size()
+            cap = sum(self.l2_db_rows(int(q)) for q in pr[:, 0] if 0 <= q < size)
+        out = np.zeros(max(cap, 1), DMATCH_DTYPE)
+        offs = np.zeros(n + 1, np.uintp)
+        _check(self._lib.lcm_l2_db_match_pairs_ratio(self._h, _ptr(pr), n, ratio, out.ctypes.data_as(_vp), cap,
+                                                     offs.ctypes.data_as(_vp)))
+        return [out[int(offs[i]): int(offs[i + 1])] for i in range(n)], offs
+
+    def _l2_db_search_args(self, skip, ratio, min_rows, min_matches, cap, out):
+        rp = _ratio_loop_params(ratio, min_rows, min_matches)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+        assert sk is None or sk.shape == (self.l2_db_size(),)
+        if out is None:
+            cap = max(self.l2_db_size(), 1) ** 2 if cap is None else cap
+            out = np.zeros(max(cap, 1), CANDIDATE_DTYPE)
+        else:
+            assert out.dtype == CANDIDATE_DTYPE and out.flags["C_CONTIGUOUS"]
+            cap = len(out) if cap is None else cap
+        return (None if rp is None else C.byref(rp)), rp, sk, cap, out
+
+    def l2_db_loop_search(self, loop_gap: int, skip=None, ratio: Optional[float] = None, min_rows: Optional[int] = None,
+                          min_matches: Optional[int] = None, cap: Optional[int] = None,
+                          out: Optional[np.ndarray] = None) -> Tuple[np.ndarray, int]:
+        """loop_search_ratio_l2 over the stored slots: (candidates in (curr, past) order, pairs scored).  skip: optional
+        flags, one per slot."""
+        rpp, _rp, sk, cap, out = self._l2_db_search_args(skip, ratio, min_rows, min_matches, cap, out)
+        n, npairs = C.c_size_t(0), C.c_size_t(0)
+        _check(self._lib.lcm_l2_db_loop_search(self._h, _ptr(sk), loop_gap, rpp, out.ctypes.data_as(_vp), cap, C.byref(n),
+                                               C.byref(npairs)))
+        return out[: n.value], npairs.value
+
+    def l2_db_detect_loops(self, curr: int, loop_gap: int, query=None, skip=None, ratio: Optional[float] = None,
+                           min_rows: Optional[int] = None, min_matches: Optional[int] = None, cap: Optional[int] = None,
+                           out: Optional[np.ndarray] = None) -> Tuple[np.ndarray, int]:
+        """One keyframe against the stored slots [0, curr - loop_gap]: (candidates, pairs scored).  query: host SIFT rows
+        standing for position `curr` (not stored), or None for the stored slot `curr`."""
+        rpp, _rp, sk, cap, out = self._l2_db_search_args(skip, ratio, min_rows, min_matches, cap, out)
+        q = None if query is None else _sift_rows(query)
+        # an empty host matrix is still the host form: the library tells the two apart by the pointer
+        qp = None if q is None else (q if q.size else np.zeros((1, SIFT_BYTES), np.uint8)).ctypes.data_as(_vp)
+        n, npairs = C.c_size_t(0), C.c_size_t(0)
+        _check(self._lib.lcm_l2_db_detect_loops(self._h, curr, qp, 0 if q is None else q.shape[0], _ptr(sk), loop_gap, rpp,
+                                                out.ctypes.data_as(_vp), cap, C.byref(n), C.byref(npairs)))
+        return out[: n.value], npairs.value
 
     # -- loop search -------------------------------------------------------------------------------
     def query_scores(self, query, query_frame_id: int) -> Tuple[np.ndarray, np.ndarray]:

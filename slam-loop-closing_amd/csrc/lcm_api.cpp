@@ -225,6 +225,8 @@ void lcm_destroy(lcm_handle* h) {
     if (h->l2.h_fin) (void)hipHostFree(h->l2.h_fin);
     (void)hipFree(h->l2.d_score); (void)hipFree(h->l2.d_diag);
     if (h->l2.h_score) (void)hipHostFree(h->l2.h_score);
+    (void)hipFree(h->l2db.d_raw); (void)hipFree(h->l2db.d_img); (void)hipFree(h->l2db.d_tw); (void)hipFree(h->l2db.d_frames);
+    (void)hipFree(h->l2db.d_meta); (void)hipFree(h->l2db.d_tab);
     for (QuerySlot& q : h->qslots) {
         (void)hipFree(q.d_query); (void)hipFree(q.d_scores); (void)hipFree(q.d_dist); (void)hipFree(q.d_meta);
         if (q.h_meta) (void)hipHostFree(q.h_meta);

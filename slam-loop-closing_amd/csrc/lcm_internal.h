@@ -5,7 +5,8 @@
 //   lcm_mfma_host.cpp  opt-in matrix-core variants    lcm_group.cpp    multi-GPU group (RCCL)
 //   lcm_knn.cpp        pair mode with k = 2 neighbours + Lowe's ratio test
 //   lcm_ratio.cpp      bulk / online loop search scored with Lowe's ratio test
-//   lcm_l2.cpp         pair mode on 128-byte SIFT rows under L2 (knnMatch(k = 2) + ratio test), ratio-test counts per pair
+//   lcm_l2.cpp         pair mode on 128-byte SIFT rows under L2 (knnMatch(k = 2) + ratio test), ratio-test counts per pair,
+//                      the SIFT keyframe store (lcm_l2_db_*)
 // Not installed; the public surface is include/lcm.h.
 #pragma once
 #include "../../include/lcm.h"
@@ -240,6 +241,18 @@ struct lcm_handle {
         lcm_l2_score* h_score = nullptr; size_t h_score_n = 0;
         uint32_t* d_diag = nullptr; size_t d_diag_n = 0;
     } l2;
+    // the SIFT keyframe store (lcm_l2_db_*, lcm_l2.cpp): three arenas in ONE tile space (lcm_kernels.h) with room for
+    // cap_tiles tiles, slot f's frame at tile tile0[f] (tile0 has size + 1 entries: the last is the first free tile), the
+    // device frame table {first tile, rows} per slot, and the tables of the last search
+    struct L2Store {
+        uint8_t* d_raw = nullptr;  uint8_t* d_img = nullptr;  uint32_t* d_tw = nullptr;  size_t cap_tiles = 0;
+        uint2* d_frames = nullptr; size_t d_frames_cap = 0;
+        uint32_t* d_meta = nullptr; size_t d_meta_n = 0;       // k_l2_pack's tile words of the tiles being packed
+        uint8_t* d_tab = nullptr;  size_t d_tab_n = 0;         // a search's [runs | admitted slots]
+        std::vector<uint32_t> tile0{0};
+        std::vector<int> rows;
+        size_t last_table_bytes = 0;
+    } l2db;
     lcm_launch_info info{};
     bool info_pending = false;
 };

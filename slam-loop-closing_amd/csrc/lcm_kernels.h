@@ -225,6 +225,27 @@ hipError_t launch_l2_count(const L2CountArgs& a, uint32_t n_items, hipStream_t s
 // pass[i] = the count kernel's verdict on (d1[i], d2[i]), both <= L2_MAX_DSQ: one thread each, grid-stride
 hipError_t launch_l2_ratio_test(const uint32_t* d1, const uint32_t* d2, size_t n, double ratio, uint8_t* pass, hipStream_t st);
 
+// ---- the same counts over the SIFT keyframe store (lcm_l2_store.hip): no per-item table ------------------------------------
+// The store keeps every appended matrix in the tile space above and a device FRAME TABLE {first tile, rows} per slot.  A
+// search is a list of RUNS: one query matrix (a stored slot, or host rows staged in the arena's free tail) against the
+// first n_past entries of `past`, ONE ascending list of admitted stored slots that all runs share.  Run u owns workgroups
+// [first_wg, first_wg + n_past * chunks): local workgroup l scores chunk l % chunks of the query against slot
+// past[l / chunks] (the chunks of a pair are adjacent: they share the train tiles in L2) into scores[first_pair + l / chunks].
+// The workgroup finds its run by a binary search over first_wg (strictly ascending: every run has at least one workgroup).
+struct L2StoreRun { uint32_t q_tile, q_rows, chunks, first_wg, first_pair, n_past; };      // 24 bytes
+struct L2StoreArgs {
+    const uint8_t*    img;
+    const uint32_t*   tw;
+    const L2StoreRun* runs;
+    const uint32_t*   past;        // admitted stored slots with at least one row, ascending
+    const uint2*      frames;      // the store's frame table: (first tile, rows) per slot
+    uint2*            scores;      // (good_count, min_dist_sq) per pair, initialised by launch_l2_count_init
+    double            ratio;
+    uint32_t          n_runs;
+    uint32_t          chunk_rows;  // 128 (one query tile per wave) or 256 (two)
+};
+hipError_t launch_l2_count_store(const L2StoreArgs& a, uint32_t n_workgroups, hipStream_t st);
+
 // ---- bulk / online loop search scored with Lowe's ratio test (lcm_ratio.hip): src/main.cpp:1375-1388 -------------------
 // One workgroup = one WorkItem (or an implicit run of stored slots for ONE query frame, as ScoreArgs' implicit items):
 // per pair, good_count = number of query rows with best < ratio * second (knnMatch(k = 2) order, the second smallest

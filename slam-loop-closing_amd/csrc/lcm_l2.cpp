@@ -4,7 +4,8 @@
 // squared distances into OpenCV's float distances (sqrtf, correctly rounded on the host) and runs the ratio test in IEEE
 // double.  The loop search's form (lcm_score_pairs_ratio_l2, lcm_loop_search_ratio_l2) wants the survivor COUNT per pair
 // only: lcm_l2_count.hip scores a pair's whole train matrix in one workgroup per query chunk and decides on the device, so
-// 8 bytes per pair come back.  Part of liblcm_hip.so's host side (C ABI in include/lcm.h); shared state and helpers:
+// 8 bytes per pair come back.  The SIFT keyframe store (lcm_l2_db_*) keeps uploaded and packed matrices on the device and
+// searches them from tables that grow with the frames (lcm_l2_store.hip).  Part of liblcm_hip.so's host side (C ABI in include/lcm.h); shared state and helpers:
 // lcm_internal.h.
 #include "lcm_internal.h"
 
@@ -18,6 +19,7 @@ constexpr int TILE = lcm::L2_TILE_ROWS, SEG = lcm::L2_SEG_ROWS, ROW = LCM_SIFT_B
 static_assert(LCM_SIFT_BYTES == lcm::L2_ROW_BYTES, "row size");
 
 struct L2Pair { int q, t; };                // positions into the call's matrices, both sides non-empty
+using L2Store = lcm_handle::L2Store;        // the SIFT keyframe store, below
 
 // What every k = 2 call refuses (lcm_knn.cpp's rule)
 int check_knn(const lcm_handle* h, double ratio) {
@@ -55,8 +57,10 @@ void tile_space(const int* rows, int n_frames, std::vector<uint32_t>& tile0, std
 
 // Uploads every matrix once, packs, scores every pair, folds, rescans: (D1, idx1, D2, idx2) per query row of pair p at
 // (*fin)[4 * (row0[p] + r)], in pinned host memory that stays valid until the next L2 call on this handle.
+// db != NULL: the matrices are the store's slots (rows = db->rows): nothing is uploaded or packed, the items point into
+// the store's arenas.
 int l2_run(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_frames, const std::vector<L2Pair>& pairs,
-           const uint32_t** fin, std::vector<size_t>& row0) {
+           const uint32_t** fin, std::vector<size_t>& row0, const L2Store* db = nullptr) {
     int rc = set_device(h); if (rc) return rc;
     const size_t P = pairs.size();
     row0.assign(P + 1, 0);
@@ -64,7 +68,8 @@ int l2_run(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_f
     if (P == 0) return LCM_OK;
 
     std::vector<uint32_t> tile0, tile_meta;
-    tile_space(rows, n_frames, tile0, tile_meta);
+    if (db) tile0 = db->tile0;
+    else tile_space(rows, n_frames, tile0, tile_meta);
     const size_t n_tiles = tile_meta.size();
 
     // ---- items and jobs
@@ -103,9 +108,14 @@ int l2_run(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_f
     memcpy(tab.data(), tile_meta.data(), n_tiles * sizeof(uint32_t));
     memcpy(tab.data() + off_items, items.data(), n_items * sizeof(lcm::L2Item));
     memcpy(tab.data() + off_jobs, jobs.data(), P * sizeof(lcm::L2Job));
-    rc = ensure_dev(s.d_raw, s.d_raw_n, n_tiles * (size_t)lcm::L2_TILE_BYTES); if (rc) return rc;
-    rc = ensure_dev(s.d_img, s.d_img_n, n_tiles * (size_t)lcm::L2_TILE_BYTES); if (rc) return rc;
-    rc = ensure_dev(s.d_tw, s.d_tw_n, n_tiles * (size_t)TILE); if (rc) return rc;
+    if (!db) {
+        rc = ensure_dev(s.d_raw, s.d_raw_n, n_tiles * (size_t)lcm::L2_TILE_BYTES); if (rc) return rc;
+        rc = ensure_dev(s.d_img, s.d_img_n, n_tiles * (size_t)lcm::L2_TILE_BYTES); if (rc) return rc;
+        rc = ensure_dev(s.d_tw, s.d_tw_n, n_tiles * (size_t)TILE); if (rc) return rc;
+    }
+    const uint8_t* d_raw = db ? db->d_raw : s.d_raw;
+    const uint8_t* d_img = db ? db->d_img : s.d_img;
+    const uint32_t* d_tw = db ? db->d_tw : s.d_tw;
     rc = ensure_dev(s.d_tab, s.d_tab_n, tab_bytes); if (rc) return rc;
     rc = ensure_dev(s.d_seg, s.d_seg_n, n_items * (size_t)CH); if (rc) return rc;
     rc = ensure_dev(s.d_fin, s.d_fin_n, total_rows); if (rc) return rc;
@@ -113,25 +123,28 @@ int l2_run(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_f
     rc = ensure_pinned(s.h_fin, s.h_fin_n, total_rows); if (rc) return rc;
 
     // The sources are pageable: they stay alive (and unchanged) until the synchronisation at the end of this function.
-    for (int f = 0; f < n_frames; ++f)
+    for (int f = 0; f < n_frames && !db; ++f)
         if (rows[f] > 0)
             HIP_TRY(hipMemcpyAsync(s.d_raw + (size_t)tile0[(size_t)f] * lcm::L2_TILE_BYTES, frames[f], (size_t)rows[f] * ROW,
                                    hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(s.d_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, h->stream));
 
-    const lcm::L2PackArgs pa{s.d_raw, reinterpret_cast<const uint32_t*>(s.d_tab), s.d_img, s.d_tw, (uint32_t)n_tiles};
-    hipError_t e = lcm::launch_l2_pack(pa, h->stream);
-    if (e != hipSuccess) return fail(LCM_ERR_HIP, "pack kernel launch failed: %s", hipGetErrorString(e));
-    const lcm::L2ScoreArgs sa{s.d_img, s.d_tw, reinterpret_cast<const lcm::L2Item*>(s.d_tab + off_items), s.d_seg, (uint32_t)CH};
+    hipError_t e = hipSuccess;
+    if (!db) {
+        const lcm::L2PackArgs pa{s.d_raw, reinterpret_cast<const uint32_t*>(s.d_tab), s.d_img, s.d_tw, (uint32_t)n_tiles};
+        e = lcm::launch_l2_pack(pa, h->stream);
+        if (e != hipSuccess) return fail(LCM_ERR_HIP, "pack kernel launch failed: %s", hipGetErrorString(e));
+    }
+    const lcm::L2ScoreArgs sa{d_img, d_tw, reinterpret_cast<const lcm::L2Item*>(s.d_tab + off_items), s.d_seg, (uint32_t)CH};
     HIP_TRY(hipEventRecord(h->ev_start, h->stream));
     e = lcm::launch_l2_score(sa, (uint32_t)n_items, h->stream);
     if (e != hipSuccess) return fail(LCM_ERR_HIP, "score kernel launch failed: %s", hipGetErrorString(e));
     HIP_TRY(hipEventRecord(h->ev_stop, h->stream));
     h->info_pending = true;
-    h->info.workgroups = (uint32_t)n_items; h->info.route = LCM_ROUTE_PLAIN; h->info.launches = 4;
+    h->info.workgroups = (uint32_t)n_items; h->info.route = LCM_ROUTE_PLAIN; h->info.launches = db ? 3 : 4;
     h->info.pairs = P; h->info.distances = distances; h->info.algo_bytes = 2 * n_tiles * (uint64_t)lcm::L2_TILE_BYTES + total_rows * 16;
     const lcm::L2FoldArgs fa{s.d_seg, (uint32_t)CH, reinterpret_cast<const lcm::L2Job*>(s.d_tab + off_jobs), s.d_fin,
-                             reinterpret_cast<uint32_t*>(s.d_tab + off_counter), s.d_flag, (uint32_t)total_rows, s.d_raw, 0};
+                             reinterpret_cast<uint32_t*>(s.d_tab + off_counter), s.d_flag, (uint32_t)total_rows, d_raw, 0};
     e = lcm::launch_l2_fold(fa, (uint32_t)P, (uint32_t)max_nq, h->stream);
     if (e != hipSuccess) return fail(LCM_ERR_HIP, "fold kernel launch failed: %s", hipGetErrorString(e));
     e = lcm::launch_l2_rescan(fa, h->stream);
@@ -203,13 +216,14 @@ int match_features_ratio_l2_impl(lcm_handle* h, const uint8_t* query, int nq, co
     return LCM_OK;
 }
 
+// db != NULL: the matrices are the store's slots (frames unused, rows / n_frames the store's)
 int match_pairs_ratio_l2_impl(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_frames, const lcm_pair_ref* pairs,
-                              int n_pairs, double ratio, lcm_dmatch* out, size_t cap, size_t* offsets) {
-    if (!h || n_frames < 0 || n_pairs < 0 || !offsets || (n_frames > 0 && (!frames || !rows)) || (n_pairs > 0 && !pairs))
+                              int n_pairs, double ratio, lcm_dmatch* out, size_t cap, size_t* offsets, const L2Store* db = nullptr) {
+    if (!h || n_frames < 0 || n_pairs < 0 || !offsets || (!db && n_frames > 0 && (!frames || !rows)) || (n_pairs > 0 && !pairs))
         return fail(LCM_ERR_INVALID_ARG, "bad argument");
     offsets[0] = 0;
     int rc = check_knn(h, ratio); if (rc) return rc;
-    for (int f = 0; f < n_frames; ++f) {
+    for (int f = 0; f < n_frames && !db; ++f) {
         rc = check_rows(rows[f]); if (rc) return rc;
         if (rows[f] > 0 && !frames[f]) return fail(LCM_ERR_INVALID_ARG, "matrix %d is NULL", f);
     }
@@ -224,7 +238,7 @@ int match_pairs_ratio_l2_impl(lcm_handle* h, const uint8_t* const* frames, const
     }
     const uint32_t* fin = nullptr;
     std::vector<size_t> row0;
-    rc = l2_run(h, frames, rows, n_frames, live, &fin, row0); if (rc) return rc;
+    rc = l2_run(h, frames, rows, n_frames, live, &fin, row0, db); if (rc) return rc;
     // sizes first: a too-small `cap` is refused before anything is written
     std::vector<size_t> count((size_t)n_pairs, 0);
     size_t total = 0;
@@ -248,17 +262,21 @@ int match_pairs_ratio_l2_impl(lcm_handle* h, const uint8_t* const* frames, const
 // ---- ratio-test counts per pair (lcm_l2_count.hip) ------------------------------------------------------------------------
 // Query chunk of a count item: the rule of pick_chunk_rows on this kernel's items (one per query chunk of a pair, whatever
 // the train matrix's size).  LCM_TUNE_L2_COUNT_CHUNK = 128 | 256 pins it (tools/l2_count_time.py measures both).
-int pick_count_chunk_rows(const std::vector<L2Pair>& pairs, const int* rows) {
+int count_chunk_rows(size_t items256) {      // items256: the call's items at 256 rows per chunk
     if (const char* e = getenv("LCM_TUNE_L2_COUNT_CHUNK")) { const int v = atoi(e); if (v == 128 || v == 256) return v; }
+    return items256 < 1024 ? 128 : 256;
+}
+int pick_count_chunk_rows(const std::vector<L2Pair>& pairs, const int* rows) {
     size_t items256 = 0;
     for (const L2Pair& p : pairs) items256 += (size_t)((rows[p.q] + 255) / 256);
-    return items256 < 1024 ? 128 : 256;
+    return count_chunk_rows(items256);
 }
 
 // Uploads the matrices that a live pair names (once each), packs, counts: live[j]'s record -> (*rec)[j], in pinned host
 // memory that stays valid until the next count call on this handle.  Both sides of every live pair are non-empty.
+// db != NULL: the matrices are the store's slots, as in l2_run.
 int l2_count_run(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_frames, const std::vector<L2Pair>& live,
-                 double ratio, const lcm_l2_score** rec) {
+                 double ratio, const lcm_l2_score** rec, const L2Store* db = nullptr) {
     int rc = set_device(h); if (rc) return rc;
     *rec = nullptr;
     const size_t P = live.size();
@@ -268,7 +286,8 @@ int l2_count_run(lcm_handle* h, const uint8_t* const* frames, const int* rows, i
     std::vector<int> used_rows((size_t)n_frames, 0);            // a matrix in no live pair takes no room in the tile space
     for (const L2Pair& p : live) { used_rows[(size_t)p.q] = rows[p.q]; used_rows[(size_t)p.t] = rows[p.t]; }
     std::vector<uint32_t> tile0, tile_meta;
-    tile_space(used_rows.data(), n_frames, tile0, tile_meta);
+    if (db) tile0 = db->tile0;
+    else tile_space(used_rows.data(), n_frames, tile0, tile_meta);
     const size_t n_tiles = tile_meta.size();
 
     const int CH = pick_count_chunk_rows(live, rows);
@@ -295,32 +314,37 @@ int l2_count_run(lcm_handle* h, const uint8_t* const* frames, const int* rows, i
     std::vector<uint8_t> tab(tab_bytes, 0);
     memcpy(tab.data(), tile_meta.data(), n_tiles * sizeof(uint32_t));
     memcpy(tab.data() + off_items, items.data(), n_items * sizeof(lcm::L2CountItem));
-    rc = ensure_dev(s.d_raw, s.d_raw_n, n_tiles * (size_t)lcm::L2_TILE_BYTES); if (rc) return rc;
-    rc = ensure_dev(s.d_img, s.d_img_n, n_tiles * (size_t)lcm::L2_TILE_BYTES); if (rc) return rc;
-    rc = ensure_dev(s.d_tw, s.d_tw_n, n_tiles * (size_t)TILE); if (rc) return rc;
+    if (!db) {
+        rc = ensure_dev(s.d_raw, s.d_raw_n, n_tiles * (size_t)lcm::L2_TILE_BYTES); if (rc) return rc;
+        rc = ensure_dev(s.d_img, s.d_img_n, n_tiles * (size_t)lcm::L2_TILE_BYTES); if (rc) return rc;
+        rc = ensure_dev(s.d_tw, s.d_tw_n, n_tiles * (size_t)TILE); if (rc) return rc;
+    }
     rc = ensure_dev(s.d_tab, s.d_tab_n, tab_bytes); if (rc) return rc;
     rc = ensure_dev(s.d_score, s.d_score_n, P); if (rc) return rc;
     rc = ensure_pinned(s.h_score, s.h_score_n, P); if (rc) return rc;
 
     // The sources are pageable: they stay alive (and unchanged) until the synchronisation at the end of this function.
-    for (int f = 0; f < n_frames; ++f)
+    for (int f = 0; f < n_frames && !db; ++f)
         if (used_rows[(size_t)f] > 0)
             HIP_TRY(hipMemcpyAsync(s.d_raw + (size_t)tile0[(size_t)f] * lcm::L2_TILE_BYTES, frames[f], (size_t)rows[f] * ROW,
                                    hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(s.d_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, h->stream));
 
-    const lcm::L2PackArgs pa{s.d_raw, reinterpret_cast<const uint32_t*>(s.d_tab), s.d_img, s.d_tw, (uint32_t)n_tiles};
-    hipError_t e = lcm::launch_l2_pack(pa, h->stream);
-    if (e != hipSuccess) return fail(LCM_ERR_HIP, "pack kernel launch failed: %s", hipGetErrorString(e));
+    hipError_t e = hipSuccess;
+    if (!db) {
+        const lcm::L2PackArgs pa{s.d_raw, reinterpret_cast<const uint32_t*>(s.d_tab), s.d_img, s.d_tw, (uint32_t)n_tiles};
+        e = lcm::launch_l2_pack(pa, h->stream);
+        if (e != hipSuccess) return fail(LCM_ERR_HIP, "pack kernel launch failed: %s", hipGetErrorString(e));
+    }
     e = lcm::launch_l2_count_init(s.d_score, (uint32_t)P, h->stream);
     if (e != hipSuccess) return fail(LCM_ERR_HIP, "count init kernel launch failed: %s", hipGetErrorString(e));
-    const lcm::L2CountArgs ca{s.d_img, s.d_tw, reinterpret_cast<const lcm::L2CountItem*>(s.d_tab + off_items), s.d_score, ratio, (uint32_t)CH};
+    const lcm::L2CountArgs ca{db ? db->d_img : s.d_img, db ? db->d_tw : s.d_tw, reinterpret_cast<const lcm::L2CountItem*>(s.d_tab + off_items), s.d_score, ratio, (uint32_t)CH};
     HIP_TRY(hipEventRecord(h->ev_start, h->stream));
     e = lcm::launch_l2_count(ca, (uint32_t)n_items, h->stream);
     if (e != hipSuccess) return fail(LCM_ERR_HIP, "count kernel launch failed: %s", hipGetErrorString(e));
     HIP_TRY(hipEventRecord(h->ev_stop, h->stream));
     h->info_pending = true;
-    h->info.workgroups = (uint32_t)n_items; h->info.route = LCM_ROUTE_PLAIN; h->info.launches = 3;
+    h->info.workgroups = (uint32_t)n_items; h->info.route = LCM_ROUTE_PLAIN; h->info.launches = db ? 2 : 3;
     h->info.pairs = P; h->info.distances = distances; h->info.algo_bytes = 2 * n_tiles * (uint64_t)lcm::L2_TILE_BYTES + P * sizeof(lcm_l2_score);
     HIP_TRY(hipMemcpyAsync(s.h_score, s.d_score, P * sizeof(lcm_l2_score), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -339,12 +363,12 @@ int check_frames(const uint8_t* const* frames, const int* rows, int n_frames) {
 
 // scores[p] of every pair: live ones from the device, a pair with an empty side {0, 0xFFFFFFFF}
 int score_pairs_l2(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_frames, const std::vector<L2Pair>& pairs,
-                   double ratio, lcm_l2_score* scores) {
+                   double ratio, lcm_l2_score* scores, const L2Store* db = nullptr) {
     std::vector<L2Pair> live;
     for (const L2Pair& p : pairs)
         if (rows[p.q] > 0 && rows[p.t] > 0) live.push_back(p);
     const lcm_l2_score* rec = nullptr;
-    const int rc = l2_count_run(h, frames, rows, n_frames, live, ratio, &rec); if (rc) return rc;
+    const int rc = l2_count_run(h, frames, rows, n_frames, live, ratio, &rec, db); if (rc) return rc;
     size_t j = 0;
     for (size_t p = 0; p < pairs.size(); ++p)
         scores[p] = (rows[pairs[p].q] > 0 && rows[pairs[p].t] > 0) ? rec[j++] : lcm_l2_score{0u, NONE};
@@ -352,18 +376,18 @@ int score_pairs_l2(lcm_handle* h, const uint8_t* const* frames, const int* rows,
 }
 
 int score_pairs_ratio_l2_impl(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_frames, const lcm_pair_ref* pairs,
-                              int n_pairs, double ratio, lcm_l2_score* scores) {
-    if (!h || n_frames < 0 || n_pairs < 0 || (n_frames > 0 && (!frames || !rows)) || (n_pairs > 0 && (!pairs || !scores)))
+                              int n_pairs, double ratio, lcm_l2_score* scores, const L2Store* db = nullptr) {
+    if (!h || n_frames < 0 || n_pairs < 0 || (!db && n_frames > 0 && (!frames || !rows)) || (n_pairs > 0 && (!pairs || !scores)))
         return fail(LCM_ERR_INVALID_ARG, "bad argument");
     int rc = check_knn(h, ratio); if (rc) return rc;
-    rc = check_frames(frames, rows, n_frames); if (rc) return rc;
+    if (!db) { rc = check_frames(frames, rows, n_frames); if (rc) return rc; }
     std::vector<L2Pair> all((size_t)n_pairs);
     for (int p = 0; p < n_pairs; ++p) {
         const int q = pairs[p].query_frame_id, t = pairs[p].train_frame_id;
         if (q < 0 || q >= n_frames || t < 0 || t >= n_frames) return fail(LCM_ERR_INVALID_ARG, "pair %d: position outside [0, %d)", p, n_frames);
         all[(size_t)p] = L2Pair{q, t};
     }
-    return score_pairs_l2(h, frames, rows, n_frames, all, ratio, scores);
+    return score_pairs_l2(h, frames, rows, n_frames, all, ratio, scores, db);
 }
 
 // src/main.cpp:1375-1388 in one call: the admissible (curr, past) pairs are scored, the verdict and the compaction run
@@ -401,6 +425,287 @@ int loop_search_ratio_l2_impl(lcm_handle* h, const uint8_t* const* frames, const
                                       den > 0 ? (double)scores[p].good_count / (double)den : 0.0};
     }
     return LCM_OK;
+}
+
+// ---- the SIFT keyframe store (include/lcm.h, lcm_l2_db_*) -------------------------------------------------------------------
+// Three arenas in one tile space (lcm_kernels.h): slot f's frame occupies tiles [tile0[f], tile0[f + 1]), the tail from
+// tile0[size] on is free (a host query of lcm_l2_db_detect_loops is staged there).  k_l2_pack writes all 32 rows of every tile
+// it is given, image and words, so the pad rows of a frame's last tile are rewritten whatever a truncated frame left there
+// (the padding trap); the raw pad rows keep old bytes, which nothing reads (k_l2_rescan walks rows < nt).
+
+size_t tiles_of(int n) { return (size_t)((n + TILE - 1) / TILE); }
+
+// Room for `need` tiles: the first allocation is exactly that, later ones double.  The old blocks are freed after the copy
+// has been waited for.
+int store_reserve(lcm_handle* h, size_t need) {
+    L2Store& d = h->l2db;
+    if (need <= d.cap_tiles) return LCM_OK;
+    size_t cap = d.cap_tiles ? d.cap_tiles : need;
+    while (cap < need) cap *= 2;
+    uint8_t *raw = nullptr, *img = nullptr;
+    uint32_t* tw = nullptr;
+    auto drop = [&] { (void)hipFree(raw); (void)hipFree(img); (void)hipFree(tw); };
+    hipError_t e = hipMalloc((void**)&raw, cap * (size_t)lcm::L2_TILE_BYTES);
+    if (e == hipSuccess) e = hipMalloc((void**)&img, cap * (size_t)lcm::L2_TILE_BYTES);
+    if (e == hipSuccess) e = hipMalloc((void**)&tw, cap * (size_t)TILE * sizeof(uint32_t));
+    if (e != hipSuccess) { drop(); return fail(e == hipErrorOutOfMemory ? LCM_ERR_OOM : LCM_ERR_HIP, "store arena of %zu tiles: %s", cap, hipGetErrorString(e)); }
+    const size_t used = d.tile0.back();
+    if (used) {
+        e = hipMemcpyAsync(raw, d.d_raw, used * (size_t)lcm::L2_TILE_BYTES, hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(img, d.d_img, used * (size_t)lcm::L2_TILE_BYTES, hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(tw, d.d_tw, used * (size_t)TILE * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { drop(); return fail(LCM_ERR_HIP, "store arena copy failed: %s", hipGetErrorString(e)); }
+    (void)hipFree(d.d_raw); (void)hipFree(d.d_img); (void)hipFree(d.d_tw);
+    d.d_raw = raw; d.d_img = img; d.d_tw = tw; d.cap_tiles = cap;
+    return LCM_OK;
+}
+
+// n rows -> tiles [first, first + tiles_of(n)) of the arenas: upload + pack, enqueued on the stream (the caller waits).
+// `meta` is the caller's: it is read by the copy until then.
+int store_put(lcm_handle* h, const uint8_t* rows, int n, size_t first, std::vector<uint32_t>& meta) {
+    L2Store& d = h->l2db;
+    const size_t nt = tiles_of(n);
+    if (nt == 0) return LCM_OK;
+    meta.resize(nt);
+    for (size_t k = 0; k < nt; ++k) meta[k] = (uint32_t)std::min(TILE, n - (int)k * TILE) | ((uint32_t)k << 8);
+    int rc = ensure_dev(d.d_meta, d.d_meta_n, nt); if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(d.d_raw + first * lcm::L2_TILE_BYTES, rows, (size_t)n * ROW, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d.d_meta, meta.data(), nt * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    const lcm::L2PackArgs pa{d.d_raw + first * lcm::L2_TILE_BYTES, d.d_meta, d.d_img + first * lcm::L2_TILE_BYTES, d.d_tw + first * TILE, (uint32_t)nt};
+    const hipError_t e = lcm::launch_l2_pack(pa, h->stream);
+    if (e != hipSuccess) return fail(LCM_ERR_HIP, "pack kernel launch failed: %s", hipGetErrorString(e));
+    return LCM_OK;
+}
+
+int l2_db_append_impl(lcm_handle* h, const uint8_t* rows, int n, int* slot) {
+    if (!h) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+    int rc = check_rows(n); if (rc) return rc;
+    if (n > 0 && !rows) return fail(LCM_ERR_INVALID_ARG, "NULL buffer");
+    L2Store& d = h->l2db;
+    if (d.rows.size() >= 0x7FFFFFFFull) return fail(LCM_ERR_CAPACITY, "too many stored frames");
+    rc = set_device(h); if (rc) return rc;
+    const size_t first = d.tile0.back(), n_slots = d.rows.size();
+    rc = store_reserve(h, std::max<size_t>(first + tiles_of(n), 1)); if (rc) return rc;
+    if (n_slots + 1 > d.d_frames_cap) {          // the frame table doubles too; it is rebuilt from the host's copy
+        size_t cap = std::max<size_t>(d.d_frames_cap * 2, 64);
+        std::vector<uint2> all(n_slots);
+        for (size_t f = 0; f < n_slots; ++f) all[f] = make_uint2(d.tile0[f], (uint32_t)d.rows[f]);
+        uint2* t = nullptr;
+        HIP_TRY(hipMalloc((void**)&t, cap * sizeof(uint2)));
+        hipError_t e = n_slots ? hipMemcpyAsync(t, all.data(), n_slots * sizeof(uint2), hipMemcpyHostToDevice, h->stream) : hipSuccess;
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) { (void)hipFree(t); return fail(LCM_ERR_HIP, "frame table copy failed: %s", hipGetErrorString(e)); }
+        (void)hipFree(d.d_frames);
+        d.d_frames = t; d.d_frames_cap = cap;
+    }
+    std::vector<uint32_t> meta;
+    rc = store_put(h, rows, n, first, meta); if (rc) return rc;
+    const uint2 entry = make_uint2((uint32_t)first, (uint32_t)n);
+    HIP_TRY(hipMemcpyAsync(d.d_frames + n_slots, &entry, sizeof(entry), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));     // the caller's rows (pageable) have been consumed
+    d.rows.push_back(n);
+    d.tile0.push_back((uint32_t)(first + tiles_of(n)));
+    if (slot) *slot = (int)n_slots;
+    return LCM_OK;
+}
+
+int check_slot(const lcm_handle* h, int slot) {
+    if (slot < 0 || (size_t)slot >= h->l2db.rows.size()) return fail(LCM_ERR_INVALID_ARG, "slot %d outside [0, %zu)", slot, h->l2db.rows.size());
+    return LCM_OK;
+}
+
+int l2_db_read_impl(lcm_handle* h, int slot, uint8_t* out, int cap_rows) {
+    if (!h) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+    int rc = check_slot(h, slot); if (rc) return rc;
+    const L2Store& d = h->l2db;
+    const int n = d.rows[(size_t)slot];
+    if (cap_rows < n) return fail(LCM_ERR_CAPACITY, "slot %d holds %d rows but the buffer %d", slot, n, cap_rows);
+    if (n == 0) return LCM_OK;
+    if (!out) return fail(LCM_ERR_INVALID_ARG, "NULL buffer");
+    rc = set_device(h); if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, d.d_raw + (size_t)d.tile0[(size_t)slot] * lcm::L2_TILE_BYTES, (size_t)n * ROW, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return LCM_OK;
+}
+
+int l2_db_truncate_impl(lcm_handle* h, int n_frames) {
+    if (!h || n_frames < 0) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+    L2Store& d = h->l2db;
+    if ((size_t)n_frames > d.rows.size()) return fail(LCM_ERR_INVALID_ARG, "cannot truncate %zu frames to %d", d.rows.size(), n_frames);
+    d.rows.resize((size_t)n_frames);
+    d.tile0.resize((size_t)n_frames + 1);
+    return LCM_OK;
+}
+
+int l2_db_info_impl(lcm_handle* h, lcm_l2_db_info* out) {
+    if (!h || !out) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+    const L2Store& d = h->l2db;
+    *out = lcm_l2_db_info{(int32_t)d.rows.size(), 0, d.tile0.back(), d.cap_tiles,
+                          d.cap_tiles * (2 * (uint64_t)lcm::L2_TILE_BYTES + TILE * sizeof(uint32_t)) + d.d_frames_cap * sizeof(uint2),
+                          d.last_table_bytes};
+    return LCM_OK;
+}
+
+// One `curr` of a store search: the query matrix (tile, rows) and its admissible pasts = the admitted slots <= last_past
+struct StoreCurr { int id; uint32_t q_tile; int q_rows; int last_past; };
+
+// src/main.cpp:1375-1388 over the store, `currs` in ascending order.  A pair is (curr, admitted past slot <= last_past), in
+// that order, as lcm_loop_search_ratio_l2 forms them; the pairs with two non-empty sides are scored by k_l2_count_store
+// from [runs | live admitted slots], the others are {0, 0xFFFFFFFF} as there.  The verdict and the compaction run here over
+// the 8-byte records.
+int store_search(lcm_handle* h, const std::vector<StoreCurr>& currs, const uint8_t* skip, const lcm_ratio_loop_params& rp,
+                 lcm_loop_candidate* out, size_t cap, size_t* n_out, size_t* n_pairs_out) {
+    L2Store& d = h->l2db;
+    const size_t S = d.rows.size();
+    // admitted[0..): every admitted slot, ascending; live_before[f] = admitted slots below f that have rows (the pair's record)
+    std::vector<uint32_t> admitted, live;
+    std::vector<uint32_t> adm_before(S + 1, 0), live_before(S + 1, 0);
+    for (size_t f = 0; f < S; ++f) {
+        const bool adm = !(skip && skip[f]) && d.rows[f] >= rp.min_rows;
+        adm_before[f + 1] = adm_before[f] + (adm ? 1u : 0u);
+        live_before[f + 1] = live_before[f] + (adm && d.rows[f] > 0 ? 1u : 0u);
+        if (adm) admitted.push_back((uint32_t)f);
+        if (adm && d.rows[f] > 0) live.push_back((uint32_t)f);
+    }
+    std::vector<lcm::L2StoreRun> runs;
+    std::vector<size_t> run_of(currs.size(), (size_t)-1);
+    size_t items256 = 0, n_pairs = 0;
+    for (const StoreCurr& c : currs) {
+        const size_t last = (size_t)std::min<long long>(c.last_past, (long long)S - 1) + 1;      // pasts are slots [0, last)
+        if (c.last_past < 0) continue;
+        n_pairs += adm_before[last];
+        if (c.q_rows > 0) items256 += (size_t)live_before[last] * (size_t)((c.q_rows + 255) / 256);
+    }
+    const int CH = count_chunk_rows(items256);
+    uint64_t n_wg = 0, n_rec = 0, distances = 0;
+    std::vector<uint64_t> rows_before(S + 1, 0);              // rows of the live admitted slots below f
+    for (size_t f = 0; f < S; ++f) rows_before[f + 1] = rows_before[f] + (live_before[f + 1] != live_before[f] ? (uint64_t)d.rows[f] : 0);
+    for (size_t u = 0; u < currs.size(); ++u) {
+        const StoreCurr& c = currs[u];
+        if (c.last_past < 0 || c.q_rows <= 0) continue;
+        const size_t last = (size_t)std::min<long long>(c.last_past, (long long)S - 1) + 1;
+        const uint32_t np = live_before[last];
+        if (np == 0) continue;                                   // no admitted past: no run, no record
+        const uint32_t chunks = (uint32_t)((c.q_rows + CH - 1) / CH);
+        if (n_wg + (uint64_t)np * chunks > 0x7FFFFFFFull || n_rec + np > 0x7FFFFFFFull) return fail(LCM_ERR_CAPACITY, "too many pairs for one call");
+        run_of[u] = runs.size();
+        runs.push_back({c.q_tile, (uint32_t)c.q_rows, chunks, (uint32_t)n_wg, (uint32_t)n_rec, np});
+        n_wg += (uint64_t)np * chunks;
+        n_rec += np;
+        distances += (uint64_t)c.q_rows * rows_before[last];
+    }
+
+    const lcm_l2_score* rec = nullptr;
+    d.last_table_bytes = 0;
+    if (!runs.empty()) {
+        auto& s = h->l2;
+        const size_t off_past = runs.size() * sizeof(lcm::L2StoreRun);
+        const size_t tab_bytes = off_past + live.size() * sizeof(uint32_t);
+        std::vector<uint8_t> tab(tab_bytes);
+        memcpy(tab.data(), runs.data(), off_past);
+        memcpy(tab.data() + off_past, live.data(), live.size() * sizeof(uint32_t));
+        int rc = ensure_dev(d.d_tab, d.d_tab_n, tab_bytes); if (rc) return rc;
+        rc = ensure_dev(s.d_score, s.d_score_n, (size_t)n_rec); if (rc) return rc;
+        rc = ensure_pinned(s.h_score, s.h_score_n, (size_t)n_rec); if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(d.d_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, h->stream));
+        hipError_t e = lcm::launch_l2_count_init(s.d_score, (uint32_t)n_rec, h->stream);
+        if (e != hipSuccess) return fail(LCM_ERR_HIP, "count init kernel launch failed: %s", hipGetErrorString(e));
+        const lcm::L2StoreArgs sa{d.d_img, d.d_tw, reinterpret_cast<const lcm::L2StoreRun*>(d.d_tab),
+                                  reinterpret_cast<const uint32_t*>(d.d_tab + off_past), d.d_frames, s.d_score, rp.ratio,
+                                  (uint32_t)runs.size(), (uint32_t)CH};
+        HIP_TRY(hipEventRecord(h->ev_start, h->stream));
+        e = lcm::launch_l2_count_store(sa, (uint32_t)n_wg, h->stream);
+        if (e != hipSuccess) return fail(LCM_ERR_HIP, "count kernel launch failed: %s", hipGetErrorString(e));
+        HIP_TRY(hipEventRecord(h->ev_stop, h->stream));
+        h->info_pending = true;
+        h->info.workgroups = (uint32_t)n_wg; h->info.route = LCM_ROUTE_PLAIN; h->info.launches = 2;
+        h->info.pairs = n_rec; h->info.distances = distances; h->info.algo_bytes = tab_bytes + n_rec * sizeof(lcm_l2_score);
+        HIP_TRY(hipMemcpyAsync(s.h_score, s.d_score, (size_t)n_rec * sizeof(lcm_l2_score), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        rec = s.h_score;
+        d.last_table_bytes = tab_bytes;
+    }
+
+    if (n_pairs_out) *n_pairs_out = n_pairs;
+    // two passes over the records in (curr, past) order: the count, then (if it fits) the candidates
+    auto walk = [&](lcm_loop_candidate* dst) {
+        size_t found = 0;
+        for (size_t u = 0; u < currs.size(); ++u) {
+            const StoreCurr& c = currs[u];
+            if (c.last_past < 0) continue;
+            const size_t last = (size_t)std::min<long long>(c.last_past, (long long)S - 1) + 1;
+            const lcm_l2_score* r = run_of[u] == (size_t)-1 ? nullptr : rec + runs[run_of[u]].first_pair;
+            for (uint32_t k = 0; k < adm_before[last]; ++k) {
+                const uint32_t past = admitted[k];
+                const lcm_l2_score sc = (r && d.rows[past] > 0) ? r[live_before[past]] : lcm_l2_score{0u, NONE};
+                if ((long long)sc.good_count < (long long)rp.min_matches) continue;                  // :1388
+                if (dst) {
+                    const int den = std::min(c.q_rows, d.rows[past]);
+                    dst[found] = lcm_loop_candidate{c.id, (int32_t)past, (int32_t)sc.good_count,
+                                                    den > 0 ? (double)sc.good_count / (double)den : 0.0};
+                }
+                ++found;
+            }
+        }
+        return found;
+    };
+    const size_t found = walk(nullptr);
+    *n_out = found;
+    if (found > (out ? cap : 0)) return fail(LCM_ERR_CAPACITY, "%zu loop candidates but room for %zu", found, out ? cap : (size_t)0);
+    if (found) walk(out);
+    return LCM_OK;
+}
+
+// what lcm_loop_search_ratio_l2 checks before it looks at a matrix
+int store_search_args(lcm_handle* h, int loop_gap, const lcm_ratio_loop_params* rp_in, size_t* n_out, size_t* n_pairs_out,
+                      lcm_ratio_loop_params* rp) {
+    if (!h || !n_out) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+    *n_out = 0;
+    if (n_pairs_out) *n_pairs_out = 0;
+    if (loop_gap < 1) return fail(LCM_ERR_INVALID_ARG, "loop_gap must be >= 1");
+    int rc = lcm::ratio_loop_params_checked(rp_in, rp); if (rc) return rc;
+    rc = check_knn(h, rp->ratio); if (rc) return rc;
+    return set_device(h);
+}
+
+int l2_db_loop_search_impl(lcm_handle* h, const uint8_t* skip, int loop_gap, const lcm_ratio_loop_params* rp_in,
+                           lcm_loop_candidate* out, size_t cap, size_t* n_out, size_t* n_pairs_out) {
+    lcm_ratio_loop_params rp;
+    const int rc = store_search_args(h, loop_gap, rp_in, n_out, n_pairs_out, &rp); if (rc) return rc;
+    const L2Store& d = h->l2db;
+    std::vector<StoreCurr> currs;
+    for (size_t curr = (size_t)loop_gap; curr < d.rows.size(); ++curr)
+        if (!(skip && skip[curr]) && d.rows[curr] >= rp.min_rows)                                   // :1377, :1382
+            currs.push_back({(int)curr, d.tile0[curr], d.rows[curr], (int)curr - loop_gap});
+    return store_search(h, currs, skip, rp, out, cap, n_out, n_pairs_out);
+}
+
+int l2_db_detect_loops_impl(lcm_handle* h, int curr, const uint8_t* query, int nq, const uint8_t* skip, int loop_gap,
+                            const lcm_ratio_loop_params* rp_in, lcm_loop_candidate* out, size_t cap, size_t* n_out, size_t* n_pairs_out) {
+    lcm_ratio_loop_params rp;
+    int rc = store_search_args(h, loop_gap, rp_in, n_out, n_pairs_out, &rp); if (rc) return rc;
+    L2Store& d = h->l2db;
+    StoreCurr c{curr, 0, 0, 0};
+    std::vector<uint32_t> meta;
+    if (query) {
+        rc = check_rows(nq); if (rc) return rc;
+        const size_t first = d.tile0.back();
+        rc = store_reserve(h, std::max<size_t>(first + tiles_of(nq), 1)); if (rc) return rc;
+        rc = store_put(h, query, nq, first, meta); if (rc) return rc;      // `meta` and `query` live until store_search has waited
+        c.q_tile = (uint32_t)first; c.q_rows = nq;
+    } else {
+        rc = check_slot(h, curr); if (rc) return rc;
+        c.q_tile = d.tile0[(size_t)curr]; c.q_rows = d.rows[(size_t)curr];
+    }
+    const long long last = (long long)curr - loop_gap;
+    c.last_past = (int)std::max<long long>(last, -1);
+    std::vector<StoreCurr> currs;
+    if (c.q_rows >= rp.min_rows) currs.push_back(c);                        // :1382
+    rc = store_search(h, currs, skip, rp, out, cap, n_out, n_pairs_out);
+    if (query && nq > 0) HIP_TRY(hipStreamSynchronize(h->stream));          // a search that launched nothing has not waited
+    return rc;
 }
 
 int l2_ratio_test_device_impl(lcm_handle* h, const uint32_t* d1, const uint32_t* d2, size_t n, double ratio, uint8_t* pass) {
@@ -460,6 +765,44 @@ int lcm_loop_search_ratio_l2(lcm_handle* h, const uint8_t* const* frames, const 
                              int loop_gap, const lcm_ratio_loop_params* rp, lcm_loop_candidate* out, size_t cap, size_t* n_out,
                              size_t* n_pairs_out) {
     return guarded([&] { return loop_search_ratio_l2_impl(h, frames, rows, n_frames, skip, loop_gap, rp, out, cap, n_out, n_pairs_out); });
+}
+int lcm_l2_db_append(lcm_handle* h, const uint8_t* rows, int n, int* slot) {
+    return guarded([&] { return l2_db_append_impl(h, rows, n, slot); });
+}
+int lcm_l2_db_size(lcm_handle* h) { return h ? (int)h->l2db.rows.size() : 0; }
+int lcm_l2_db_rows(lcm_handle* h, int slot, int* n) {
+    if (!h || !n) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+    const int rc = check_slot(h, slot); if (rc) return rc;
+    *n = h->l2db.rows[(size_t)slot];
+    return LCM_OK;
+}
+int lcm_l2_db_read(lcm_handle* h, int slot, uint8_t* out, int cap_rows) {
+    return guarded([&] { return l2_db_read_impl(h, slot, out, cap_rows); });
+}
+int lcm_l2_db_truncate(lcm_handle* h, int n_frames) { return guarded([&] { return l2_db_truncate_impl(h, n_frames); }); }
+int lcm_l2_db_clear(lcm_handle* h) { return guarded([&] { return l2_db_truncate_impl(h, 0); }); }
+int lcm_l2_db_info_read(lcm_handle* h, lcm_l2_db_info* out) { return l2_db_info_impl(h, out); }
+int lcm_l2_db_score_pairs(lcm_handle* h, const lcm_pair_ref* slots, int n_pairs, double ratio, lcm_l2_score* scores) {
+    return guarded([&] {
+        if (!h) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+        return score_pairs_ratio_l2_impl(h, nullptr, h->l2db.rows.data(), (int)h->l2db.rows.size(), slots, n_pairs, ratio, scores, &h->l2db);
+    });
+}
+int lcm_l2_db_match_pairs_ratio(lcm_handle* h, const lcm_pair_ref* slots, int n_pairs, double ratio, lcm_dmatch* out, size_t cap,
+                                size_t* offsets) {
+    return guarded([&] {
+        if (!h) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+        return match_pairs_ratio_l2_impl(h, nullptr, h->l2db.rows.data(), (int)h->l2db.rows.size(), slots, n_pairs, ratio, out, cap, offsets,
+                                         &h->l2db);
+    });
+}
+int lcm_l2_db_loop_search(lcm_handle* h, const uint8_t* skip, int loop_gap, const lcm_ratio_loop_params* rp, lcm_loop_candidate* out,
+                          size_t cap, size_t* n_out, size_t* n_pairs_out) {
+    return guarded([&] { return l2_db_loop_search_impl(h, skip, loop_gap, rp, out, cap, n_out, n_pairs_out); });
+}
+int lcm_l2_db_detect_loops(lcm_handle* h, int curr, const uint8_t* query, int nq, const uint8_t* skip, int loop_gap,
+                           const lcm_ratio_loop_params* rp, lcm_loop_candidate* out, size_t cap, size_t* n_out, size_t* n_pairs_out) {
+    return guarded([&] { return l2_db_detect_loops_impl(h, curr, query, nq, skip, loop_gap, rp, out, cap, n_out, n_pairs_out); });
 }
 int lcm_l2_ratio_test_device(lcm_handle* h, const uint32_t* d1, const uint32_t* d2, size_t n, double ratio, uint8_t* pass) {
     return guarded([&] { return l2_ratio_test_device_impl(h, d1, d2, n, ratio, pass); });
