@@ -403,6 +403,42 @@ LCM_API int  lcm_l2_db_detect_loops(lcm_handle* h, int curr, const uint8_t* quer
                                     const struct lcm_ratio_loop_params* rp, lcm_loop_candidate* out, size_t cap,
                                     size_t* n_out, size_t* n_pairs_out);
 
+/* ---- the store's loop correspondences: filtered, compacted and gathered on the device ---------------------------------- */
+/* src/main.cpp:1386-1392 ends with extractMatchedPoints(kp[curr], kp[past], matches, ptsCurr, ptsPast): the two point arrays
+ * findEssentialMat gets.  A frame appended WITH its keypoint coordinates keeps them in a fourth arena of the store's tile
+ * space (8 bytes per row; created when the first such frame arrives, sized, grown, truncated and cleared with the other
+ * three).  The coordinates are carried as bytes: NaN and -0.0 come back bit for bit.  The calls below run Lowe's ratio test,
+ * an ordered compaction and the keypoint gather on the device after the score, fold and rescan kernels (lcm_l2_emit.hip):
+ * 8 bytes per pair (`offsets`) come back first and decide about `cap`, then only the surviving records do.
+ * Refusals as for the rest of the family: cross_check != 0, a NaN or negative ratio, NULLs, a slot outside the store
+ * (LCM_ERR_INVALID_ARG), more than 65 535 rows (LCM_ERR_CAPACITY); ordered on the handle's stream and finished on return.
+ * lcm_last_launch_info: workgroups and kernel_ms are the score kernel's, aux_kernel_ms the count / scan / list kernels'.
+ * (The four are declared `extern`: the plain spelling is the list tests/test_l2_store_host.py pins for the calls above.) */
+typedef struct lcm_point_pair { float qx, qy, tx, ty; } lcm_point_pair;   /* 16 bytes: kp[query_idx].pt, kp[train_idx].pt */
+/* lcm_l2_db_append plus n coordinate pairs, pts = n x (x, y).  lcm_l2_db_append stores a frame WITHOUT points; a store may
+ * hold both kinds. */
+LCM_API extern int lcm_l2_db_append_kp(lcm_handle* h, const uint8_t* rows, const float* pts, int n, int* slot);
+/* The points of a slot back, bit for bit: LCM_ERR_INVALID_ARG for a slot stored without points, LCM_ERR_CAPACITY for
+ * cap_rows below the frame's rows. */
+LCM_API extern int lcm_l2_db_read_kp(lcm_handle* h, int slot, float* out, int cap_rows);
+/* `out` and `offsets` are byte for byte lcm_l2_db_match_pairs_ratio's on the same arguments; pts[i] (pts may be NULL) holds
+ * the two keypoints of out[i].  With pts every named slot that has rows must have points (LCM_ERR_INVALID_ARG otherwise,
+ * before any launch).  If the lists do not fit `cap`: LCM_ERR_CAPACITY, nothing is written to out or pts and
+ * offsets[n_pairs] holds the needed count. */
+LCM_API extern int lcm_l2_db_match_points(lcm_handle* h, const lcm_pair_ref* slots, int n_pairs, double ratio,
+                                          lcm_dmatch* out, lcm_point_pair* pts, size_t cap, size_t* offsets);
+/* One iteration of the reference's outer loop up to line 1392: cands, *n_cands, *n_pairs_out and the candidate-capacity
+ * rule are lcm_l2_db_detect_loops's; the lists (and point pairs) of the candidates follow in candidate order, candidate c in
+ * [offsets[c], offsets[c + 1]) with query = curr and train = the matched slot (offsets: cand_cap + 1 entries; only
+ * offsets[0] is written when the candidates do not fit).  query != NULL: query_pts is staged with the rows in the free tail;
+ * query_pts == NULL is allowed only with pts == NULL.  query == NULL: the stored slot curr and its own points.  With pts, a
+ * matched slot without points is LCM_ERR_INVALID_ARG.  `cap` too small: as lcm_l2_db_match_points, offsets[*n_cands] = the
+ * needed count (the candidates have been written). */
+LCM_API extern int lcm_l2_db_detect_loops_points(lcm_handle* h, int curr, const uint8_t* query, const float* query_pts, int nq,
+                                                 const uint8_t* skip, int loop_gap, const struct lcm_ratio_loop_params* rp,
+                                                 lcm_loop_candidate* cands, size_t cand_cap, size_t* n_cands, size_t* n_pairs_out,
+                                                 lcm_dmatch* out, lcm_point_pair* pts, size_t cap, size_t* offsets);
+
 /* ---- loop search against the stored database --------------------------------------------------------- */
 /* Score `query` (id query_frame_id) against every stored frame with query_frame_id - id >= min_gap, ascending
  * slot order.  out_scores / out_frame_ids need room for lcm_db_size() records. */

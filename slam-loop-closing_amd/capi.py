@@ -55,6 +55,11 @@ class RatioLoopParams(C.Structure):
     _fields_ = [("ratio", C.c_double), ("min_rows", C.c_int32), ("min_matches", C.c_int32)]
 
 
+class PointPair(C.Structure):
+    """lcm_point_pair: the keypoints of one surviving match, kp[query_idx].pt and kp[train_idx].pt."""
+    _fields_ = [("qx", C.c_float), ("qy", C.c_float), ("tx", C.c_float), ("ty", C.c_float)]
+
+
 class L2DbInfo(C.Structure):
     """lcm_l2_db_info: the SIFT keyframe store's occupancy and the table bytes of its last search."""
     _fields_ = [("frames", C.c_int32), ("reserved_", C.c_int32), ("tiles_used", C.c_uint64), ("tiles_reserved", C.c_uint64),
@@ -91,6 +96,7 @@ CANDIDATE_DTYPE = np.dtype([("current_frame_id", "<i4"), ("matched_frame_id", "<
 L2_SCORE_DTYPE = np.dtype([("good_count", "<u4"), ("min_dist_sq", "<u4")])      # lcm_l2_score
 assert SCORE_DTYPE.itemsize == C.sizeof(Score) == 8
 assert L2_SCORE_DTYPE.itemsize == 8
+assert C.sizeof(PointPair) == 16          # returned as float32[n, 4]: (qx, qy, tx, ty)
 assert DMATCH_DTYPE.itemsize == C.sizeof(DMatch) == 16
 assert CANDIDATE_DTYPE.itemsize == C.sizeof(LoopCandidate) == 24
 
@@ -152,6 +158,11 @@ _SIGNATURES = {
                                          C.POINTER(C.c_size_t)]),
     "lcm_l2_db_detect_loops": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.POINTER(RatioLoopParams), _vp, C.c_size_t,
                                           C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "lcm_l2_db_append_kp": (C.c_int, [_vp, _vp, _vp, C.c_int, _i32p]),
+    "lcm_l2_db_read_kp": (C.c_int, [_vp, C.c_int, _vp, C.c_int]),
+    "lcm_l2_db_match_points": (C.c_int, [_vp, _vp, C.c_int, C.c_double, _vp, _vp, C.c_size_t, _vp]),
+    "lcm_l2_db_detect_loops_points": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(RatioLoopParams), _vp,
+                                                 C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _vp, _vp, C.c_size_t, _vp]),
     "lcm_query_scores": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _i32p]),
     "lcm_query_submit": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _i32p]),
     "lcm_query_collect": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i32p]),
@@ -698,6 +709,91 @@ class Matcher:
         _check(self._lib.lcm_l2_db_detect_loops(self._h, curr, qp, 0 if q is None else q.shape[0], _ptr(sk), loop_gap, rpp,
                                                 out.ctypes.data_as(_vp), cap, C.byref(n), C.byref(npairs)))
         return out[: n.value], npairs.value
+
+    # -- the store's loop correspondences: ratio test, compaction and keypoint gather on the device --
+    @staticmethod
+    def _kp(pts, n: int) -> np.ndarray:
+        p = np.ascontiguousarray(pts, dtype=np.float32)
+        if p.shape != (n, 2):
+            raise ValueError(f"keypoints must be ({n}, 2) float32 (x, y), got {p.shape}")
+        return p
+
+    def l2_db_append_kp(self, rows, pts) -> int:
+        """Stores a SIFT matrix with its keypoint coordinates, float32[n, 2] of (x, y) carried bit for bit; returns its slot."""
+        r = _sift_rows(rows)
+        p = self._kp(pts, r.shape[0])
+        slot = C.c_int32(-1)
+        _check(self._lib.lcm_l2_db_append_kp(self._h, _ptr(r), _ptr(p), r.shape[0], C.byref(slot)))
+        return slot.value
+
+    def l2_db_read_kp(self, slot: int) -> np.ndarray:
+        """The keypoints of a slot stored with l2_db_append_kp, float32[n, 2]."""
+        out = np.zeros((self.l2_db_rows(slot), 2), np.float32)
+        _check(self._lib.lcm_l2_db_read_kp(self._h, slot, out.ctypes.data_as(_vp), out.shape[0]))
+        return out
+
+    def l2_db_match_points(self, pairs: Sequence[Tuple[int, int]], ratio: float, cap: Optional[int] = None, points: bool = True,
+                           out: Optional[np.ndarray] = None, pts: Optional[np.ndarray] = None):
+        """l2_db_match_pairs_ratio with the lists made on the device: (DMATCH_DTYPE[total], float32[total, 4] of (qx, qy, tx, ty)
+        or None when points is False, offsets[n + 1]).  out / pts: the caller's buffers (cap = their length unless given).
+        After LcmError(ERR_CAPACITY), `self.last_offsets[n]` holds the needed record count."""
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n = pr.shape[0]
+        if cap is None:
+            if out is not None:
+                cap = len(out)
+            else:
+                size = self.l2_db_size()
+                cap = sum(self.l2_db_rows(int(q)) for q in pr[:, 0] if 0 <= q < size)
+        if out is None:
+            out = np.zeros(max(cap, 1), DMATCH_DTYPE)
+        if points and pts is None:
+            pts = np.zeros((max(cap, 1), 4), np.float32)
+        assert out.dtype == DMATCH_DTYPE and out.flags["C_CONTIGUOUS"] and len(out) >= cap
+        assert pts is None or (pts.dtype == np.float32 and pts.flags["C_CONTIGUOUS"] and pts.shape[1:] == (4,) and len(pts) >= cap)
+        offs = np.zeros(n + 1, np.uintp)
+        self.last_offsets = offs
+        _check(self._lib.lcm_l2_db_match_points(self._h, _ptr(pr), n, ratio, out.ctypes.data_as(_vp),
+                                                None if not points else pts.ctypes.data_as(_vp), cap, offs.ctypes.data_as(_vp)))
+        total = int(offs[n])
+        return out[:total], (pts[:total] if points else None), offs
+
+    def l2_db_detect_loops_points(self, curr: int, loop_gap: int, query=None, query_pts=None, skip=None,
+                                  ratio: Optional[float] = None, min_rows: Optional[int] = None, min_matches: Optional[int] = None,
+                                  cand_cap: Optional[int] = None, cap: Optional[int] = None, points: bool = True,
+                                  cands: Optional[np.ndarray] = None, out: Optional[np.ndarray] = None,
+                                  pts: Optional[np.ndarray] = None):
+        """One keyframe against the stored slots [0, curr - loop_gap] with the candidates' match lists and keypoints:
+        (candidates, pairs scored, DMATCH_DTYPE[total], float32[total, 4] or None, offsets[n_candidates + 1]).  query /
+        query_pts: host SIFT rows and their keypoints standing for position `curr` (not stored), or None for the stored
+        slot `curr`.  After LcmError(ERR_CAPACITY), `self.last_offsets` / `self.last_n_cands` hold what the call reported."""
+        rpp, _rp, sk, cand_cap, cands = self._l2_db_search_args(skip, ratio, min_rows, min_matches, cand_cap, cands)
+        q = None if query is None else _sift_rows(query)
+        nq = 0 if q is None else q.shape[0]
+        qp = None if q is None else (q if q.size else np.zeros((1, SIFT_BYTES), np.uint8)).ctypes.data_as(_vp)
+        kp = None if (q is None or query_pts is None) else self._kp(query_pts, nq)
+        kpp = None if kp is None else (kp if kp.size else np.zeros((1, 2), np.float32)).ctypes.data_as(_vp)
+        if cap is None:
+            if out is not None:
+                cap = len(out)
+            else:
+                rows_q = nq if q is not None else (self.l2_db_rows(curr) if 0 <= curr < self.l2_db_size() else 0)
+                cap = rows_q * max(min(cand_cap, self.l2_db_size()), 1)
+        if out is None:
+            out = np.zeros(max(cap, 1), DMATCH_DTYPE)
+        if points and pts is None:
+            pts = np.zeros((max(cap, 1), 4), np.float32)
+        assert out.dtype == DMATCH_DTYPE and out.flags["C_CONTIGUOUS"] and len(out) >= cap
+        assert pts is None or (pts.dtype == np.float32 and pts.flags["C_CONTIGUOUS"] and pts.shape[1:] == (4,) and len(pts) >= cap)
+        offs = np.zeros(cand_cap + 1, np.uintp)
+        n, npairs = C.c_size_t(0), C.c_size_t(0)
+        self.last_offsets, self.last_n_cands = offs, n
+        _check(self._lib.lcm_l2_db_detect_loops_points(self._h, curr, qp, kpp, nq, _ptr(sk), loop_gap, rpp, cands.ctypes.data_as(_vp),
+                                                       cand_cap, C.byref(n), C.byref(npairs), out.ctypes.data_as(_vp),
+                                                       None if not points else pts.ctypes.data_as(_vp), cap,
+                                                       offs.ctypes.data_as(_vp)))
+        total = int(offs[n.value])
+        return cands[: n.value], npairs.value, out[:total], (pts[:total] if points else None), offs[: n.value + 1]
 
     # -- loop search -------------------------------------------------------------------------------
     def query_scores(self, query, query_frame_id: int) -> Tuple[np.ndarray, np.ndarray]:

@@ -226,7 +226,8 @@ void lcm_destroy(lcm_handle* h) {
     (void)hipFree(h->l2.d_score); (void)hipFree(h->l2.d_diag);
     if (h->l2.h_score) (void)hipHostFree(h->l2.h_score);
     (void)hipFree(h->l2db.d_raw); (void)hipFree(h->l2db.d_img); (void)hipFree(h->l2db.d_tw); (void)hipFree(h->l2db.d_frames);
-    (void)hipFree(h->l2db.d_meta); (void)hipFree(h->l2db.d_tab);
+    (void)hipFree(h->l2db.d_meta); (void)hipFree(h->l2db.d_tab); (void)hipFree(h->l2db.d_pts);
+    (void)hipFree(h->l2.d_blocks); (void)hipFree(h->l2.d_offsets); (void)hipFree(h->l2.d_rec); (void)hipFree(h->l2.d_rec_pts);
     for (QuerySlot& q : h->qslots) {
         (void)hipFree(q.d_query); (void)hipFree(q.d_scores); (void)hipFree(q.d_dist); (void)hipFree(q.d_meta);
         if (q.h_meta) (void)hipHostFree(q.h_meta);

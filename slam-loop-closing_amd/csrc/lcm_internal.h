@@ -240,12 +240,22 @@ struct lcm_handle {
         uint2* d_score = nullptr;  size_t d_score_n = 0;
         lcm_l2_score* h_score = nullptr; size_t h_score_n = 0;
         uint32_t* d_diag = nullptr; size_t d_diag_n = 0;
+        // ... and of the device-side lists (lcm_l2_emit.hip): [per-pair first block | block counts + total] as words, the
+        // per-pair offsets, the records and their point pairs
+        uint32_t* d_blocks = nullptr; size_t d_blocks_n = 0;
+        uint64_t* d_offsets = nullptr; size_t d_offsets_n = 0;
+        uint4* d_rec = nullptr;    size_t d_rec_n = 0;
+        uint4* d_rec_pts = nullptr; size_t d_rec_pts_n = 0;
     } l2;
     // the SIFT keyframe store (lcm_l2_db_*, lcm_l2.cpp): three arenas in ONE tile space (lcm_kernels.h) with room for
     // cap_tiles tiles, slot f's frame at tile tile0[f] (tile0 has size + 1 entries: the last is the first free tile), the
-    // device frame table {first tile, rows} per slot, and the tables of the last search
+    // device frame table {first tile, rows} per slot, and the tables of the last search.  A fourth arena in the same tile
+    // space, d_pts (8 bytes per row: a keypoint's x, y as bits), exists from the first frame that arrives with points
+    // (lcm_l2_db_append_kp, or a host query with points); has_pts[f] says whether slot f's rows have theirs.
     struct L2Store {
         uint8_t* d_raw = nullptr;  uint8_t* d_img = nullptr;  uint32_t* d_tw = nullptr;  size_t cap_tiles = 0;
+        uint2* d_pts = nullptr;
+        std::vector<uint8_t> has_pts;
         uint2* d_frames = nullptr; size_t d_frames_cap = 0;
         uint32_t* d_meta = nullptr; size_t d_meta_n = 0;       // k_l2_pack's tile words of the tiles being packed
         uint8_t* d_tab = nullptr;  size_t d_tab_n = 0;         // a search's [runs | admitted slots]

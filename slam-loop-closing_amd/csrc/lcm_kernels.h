@@ -189,7 +189,7 @@ hipError_t launch_l2_score(const L2ScoreArgs& a, uint32_t n_items, hipStream_t s
 // One job = one (query matrix, train matrix) pair: its items are first_item + chunk * n_seg + segment.  The fold writes
 // (D1, idx1, D2, idx2) per query row (0xFFFFFFFF = none) to final_keys[out_row0 + row] and appends the rows whose D2 is
 // >= L2_RESCAN_MIN to `flagged` (job, row), counted in *counter (zeroed by the caller); the rescan redoes those rows in
-// (sqrtf(D), index) order over the raw bytes.
+// (sqrtf(D), index) order over the raw bytes.  `reserved` is read by lcm_l2_emit.hip only: the job's first 256-row block.
 struct L2Job { uint32_t q_tile, nq, t_tile, nt, first_item, n_seg, out_row0, reserved; };
 struct L2FoldArgs {
     const uint2*    seg_keys;
@@ -245,6 +245,31 @@ struct L2StoreArgs {
     uint32_t          chunk_rows;  // 128 (one query tile per wave) or 256 (two)
 };
 hipError_t launch_l2_count_store(const L2StoreArgs& a, uint32_t n_workgroups, hipStream_t st);
+
+// ---- the ratio test, an ordered compaction and the keypoint gather over final_keys (lcm_l2_emit.hip) ----------------------
+// src/main.cpp:524-531 and :551-555 (extractMatchedPoints) for every job of a call, AFTER launch_l2_rescan (which rewrites
+// rows of final_keys).  A job's query rows are cut into BLOCKS of 256; job j's blocks are blocks[jobs[j].reserved + b], job
+// after job.  launch_l2_emit_count leaves the survivors of every block in `blocks`; launch_block_scan over n_blocks words
+// with total = blocks + n_blocks turns them into exclusive prefixes; launch_l2_emit_offsets writes the call's per-pair
+// offsets; launch_l2_emit writes survivor k of block B to out[blocks[B] + k], k = its rank in query order.
+// A record is {query row, idx1, 0, sqrtf(D1)} (lcm_dmatch); with `pts` a second 16-byte record holds the two keypoints,
+// pts[q_tile * 32 + query row] and pts[t_tile * 32 + idx1] (8 bytes per row in the store's tile space).
+struct L2EmitArgs {
+    const uint4*    final_keys;
+    const L2Job*    jobs;
+    uint32_t*       blocks;      // n_blocks + 1 words
+    const uint2*    pts;         // NULL: no point pairs
+    uint4*          out;
+    uint4*          out_pts;
+    double          ratio;
+    uint32_t        n_out;       // records `out` (and `out_pts`) hold: the scan's total
+    uint32_t        job_base;    // set by the launchers: job of blockIdx.y == 0 (slices of grid_y_limit() jobs)
+};
+hipError_t launch_l2_emit_count(const L2EmitArgs& a, uint32_t n_jobs, uint32_t max_nq, hipStream_t st);
+hipError_t launch_l2_emit(const L2EmitArgs& a, uint32_t n_jobs, uint32_t max_nq, hipStream_t st);
+// offsets[p] = blocks[pair_block[p]] for p < n: pair_block[p] = first block of the first live job at or after pair p,
+// n_blocks (the total) past the last one
+hipError_t launch_l2_emit_offsets(const uint32_t* blocks, const uint32_t* pair_block, uint64_t* offsets, uint32_t n, hipStream_t st);
 
 // ---- bulk / online loop search scored with Lowe's ratio test (lcm_ratio.hip): src/main.cpp:1375-1388 -------------------
 // One workgroup = one WorkItem (or an implicit run of stored slots for ONE query frame, as ScoreArgs' implicit items):

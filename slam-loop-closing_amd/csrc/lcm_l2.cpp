@@ -55,12 +55,23 @@ void tile_space(const int* rows, int n_frames, std::vector<uint32_t>& tile0, std
     }
 }
 
+// What l2_run leaves behind when the lists are made on the device (lcm_l2_emit.hip): final_keys stays in h->l2.d_fin
+struct L2OnDevice {
+    const lcm::L2Job* d_jobs = nullptr;     // the call's job table on the device
+    std::vector<uint32_t> first_block;      // per job: its first 256-row block (L2Job::reserved)
+    size_t n_blocks = 0;
+    int max_nq = 0;
+    std::vector<uint8_t> tab;               // the uploaded tables (pageable): alive until the caller has waited for the stream
+};
+
 // Uploads every matrix once, packs, scores every pair, folds, rescans: (D1, idx1, D2, idx2) per query row of pair p at
 // (*fin)[4 * (row0[p] + r)], in pinned host memory that stays valid until the next L2 call on this handle.
 // db != NULL: the matrices are the store's slots (rows = db->rows): nothing is uploaded or packed, the items point into
 // the store's arenas.
+// dev != NULL (with db): final_keys is not downloaded and the stream is not waited for: the kernels are enqueued, *fin stays
+// NULL and *dev says where the jobs are.
 int l2_run(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_frames, const std::vector<L2Pair>& pairs,
-           const uint32_t** fin, std::vector<size_t>& row0, const L2Store* db = nullptr) {
+           const uint32_t** fin, std::vector<size_t>& row0, const L2Store* db = nullptr, L2OnDevice* dev = nullptr) {
     int rc = set_device(h); if (rc) return rc;
     const size_t P = pairs.size();
     row0.assign(P + 1, 0);
@@ -76,7 +87,7 @@ int l2_run(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_f
     const int CH = pick_chunk_rows(pairs, rows);
     std::vector<lcm::L2Item> items;
     std::vector<lcm::L2Job> jobs(P);
-    size_t total_rows = 0;
+    size_t total_rows = 0, n_blocks = 0;
     int max_nq = 0;
     uint64_t distances = 0;
     for (size_t p = 0; p < P; ++p) {
@@ -85,7 +96,8 @@ int l2_run(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_f
         const uint32_t qt = tile0[(size_t)pairs[p].q], tt = tile0[(size_t)pairs[p].t];
         if (items.size() + (size_t)n_chunks * (size_t)n_seg > 0x7FFFFFFFull || total_rows + (size_t)nq > 0x7FFFFFFFull)
             return fail(LCM_ERR_CAPACITY, "too many pairs for one call");
-        jobs[p] = {qt, (uint32_t)nq, tt, (uint32_t)nt, (uint32_t)items.size(), (uint32_t)n_seg, (uint32_t)total_rows, 0};
+        jobs[p] = {qt, (uint32_t)nq, tt, (uint32_t)nt, (uint32_t)items.size(), (uint32_t)n_seg, (uint32_t)total_rows, (uint32_t)n_blocks};
+        n_blocks += (size_t)((nq + 255) / 256);                   // at most total_rows: fits the 32 bits
         for (int c = 0; c < n_chunks; ++c)
             for (int g = 0; g < n_seg; ++g)
                 items.push_back({qt + (uint32_t)(c * (CH / TILE)), (uint32_t)std::min(CH, nq - c * CH),
@@ -120,7 +132,7 @@ int l2_run(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_f
     rc = ensure_dev(s.d_seg, s.d_seg_n, n_items * (size_t)CH); if (rc) return rc;
     rc = ensure_dev(s.d_fin, s.d_fin_n, total_rows); if (rc) return rc;
     rc = ensure_dev(s.d_flag, s.d_flag_n, total_rows); if (rc) return rc;
-    rc = ensure_pinned(s.h_fin, s.h_fin_n, total_rows); if (rc) return rc;
+    if (!dev) { rc = ensure_pinned(s.h_fin, s.h_fin_n, total_rows); if (rc) return rc; }
 
     // The sources are pageable: they stay alive (and unchanged) until the synchronisation at the end of this function.
     for (int f = 0; f < n_frames && !db; ++f)
@@ -149,6 +161,13 @@ int l2_run(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_f
     if (e != hipSuccess) return fail(LCM_ERR_HIP, "fold kernel launch failed: %s", hipGetErrorString(e));
     e = lcm::launch_l2_rescan(fa, h->stream);
     if (e != hipSuccess) return fail(LCM_ERR_HIP, "rescan kernel launch failed: %s", hipGetErrorString(e));
+    if (dev) {
+        dev->d_jobs = fa.jobs; dev->n_blocks = n_blocks; dev->max_nq = max_nq;
+        dev->first_block.resize(P);
+        for (size_t p = 0; p < P; ++p) dev->first_block[p] = jobs[p].reserved;
+        dev->tab = std::move(tab);
+        return LCM_OK;
+    }
     HIP_TRY(hipMemcpyAsync(s.h_fin, s.d_fin, total_rows * sizeof(uint4), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     *fin = reinterpret_cast<const uint32_t*>(s.h_fin);
@@ -431,7 +450,9 @@ int loop_search_ratio_l2_impl(lcm_handle* h, const uint8_t* const* frames, const
 // Three arenas in one tile space (lcm_kernels.h): slot f's frame occupies tiles [tile0[f], tile0[f + 1]), the tail from
 // tile0[size] on is free (a host query of lcm_l2_db_detect_loops is staged there).  k_l2_pack writes all 32 rows of every tile
 // it is given, image and words, so the pad rows of a frame's last tile are rewritten whatever a truncated frame left there
-// (the padding trap); the raw pad rows keep old bytes, which nothing reads (k_l2_rescan walks rows < nt).
+// (the padding trap); the raw pad rows keep old bytes, which nothing reads (k_l2_rescan walks rows < nt).  A fourth arena,
+// 8 bytes per row, holds the keypoints of the frames that came with them (lcm_l2_db_append_kp); its pad rows keep old points,
+// which nothing reads either (k_l2_emit gathers rows < nq and train indices < nt).
 
 size_t tiles_of(int n) { return (size_t)((n + TILE - 1) / TILE); }
 
@@ -444,21 +465,40 @@ int store_reserve(lcm_handle* h, size_t need) {
     while (cap < need) cap *= 2;
     uint8_t *raw = nullptr, *img = nullptr;
     uint32_t* tw = nullptr;
-    auto drop = [&] { (void)hipFree(raw); (void)hipFree(img); (void)hipFree(tw); };
+    uint2* pts = nullptr;                                       // grows with the others once it exists
+    auto drop = [&] { (void)hipFree(raw); (void)hipFree(img); (void)hipFree(tw); (void)hipFree(pts); };
     hipError_t e = hipMalloc((void**)&raw, cap * (size_t)lcm::L2_TILE_BYTES);
     if (e == hipSuccess) e = hipMalloc((void**)&img, cap * (size_t)lcm::L2_TILE_BYTES);
     if (e == hipSuccess) e = hipMalloc((void**)&tw, cap * (size_t)TILE * sizeof(uint32_t));
+    if (e == hipSuccess && d.d_pts) e = hipMalloc((void**)&pts, cap * (size_t)TILE * sizeof(uint2));
     if (e != hipSuccess) { drop(); return fail(e == hipErrorOutOfMemory ? LCM_ERR_OOM : LCM_ERR_HIP, "store arena of %zu tiles: %s", cap, hipGetErrorString(e)); }
     const size_t used = d.tile0.back();
     if (used) {
         e = hipMemcpyAsync(raw, d.d_raw, used * (size_t)lcm::L2_TILE_BYTES, hipMemcpyDeviceToDevice, h->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(img, d.d_img, used * (size_t)lcm::L2_TILE_BYTES, hipMemcpyDeviceToDevice, h->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(tw, d.d_tw, used * (size_t)TILE * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess && pts) e = hipMemcpyAsync(pts, d.d_pts, used * (size_t)TILE * sizeof(uint2), hipMemcpyDeviceToDevice, h->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) { drop(); return fail(LCM_ERR_HIP, "store arena copy failed: %s", hipGetErrorString(e)); }
-    (void)hipFree(d.d_raw); (void)hipFree(d.d_img); (void)hipFree(d.d_tw);
-    d.d_raw = raw; d.d_img = img; d.d_tw = tw; d.cap_tiles = cap;
+    (void)hipFree(d.d_raw); (void)hipFree(d.d_img); (void)hipFree(d.d_tw); (void)hipFree(d.d_pts);
+    d.d_raw = raw; d.d_img = img; d.d_tw = tw; d.d_pts = pts; d.cap_tiles = cap;
+    return LCM_OK;
+}
+
+// The points arena, created when the first frame with points arrives (after store_reserve: cap_tiles > 0) and sized to
+// the store's capacity.  The frames stored so far have no points: nothing is copied.
+int store_pts_arena(lcm_handle* h) {
+    L2Store& d = h->l2db;
+    if (d.d_pts) return LCM_OK;
+    HIP_TRY(hipMalloc((void**)&d.d_pts, d.cap_tiles * (size_t)TILE * sizeof(uint2)));
+    return LCM_OK;
+}
+
+// n points -> rows [first * 32, first * 32 + n) of the points arena, as bytes; enqueued (the caller waits)
+int store_put_pts(lcm_handle* h, const float* pts, int n, size_t first) {
+    int rc = store_pts_arena(h); if (rc) return rc;
+    if (n > 0) HIP_TRY(hipMemcpyAsync(h->l2db.d_pts + first * TILE, pts, (size_t)n * sizeof(uint2), hipMemcpyHostToDevice, h->stream));
     return LCM_OK;
 }
 
@@ -479,10 +519,11 @@ int store_put(lcm_handle* h, const uint8_t* rows, int n, size_t first, std::vect
     return LCM_OK;
 }
 
-int l2_db_append_impl(lcm_handle* h, const uint8_t* rows, int n, int* slot) {
+// with_pts: lcm_l2_db_append_kp, `pts` = n x (x, y)
+int l2_db_append_impl(lcm_handle* h, const uint8_t* rows, int n, int* slot, bool with_pts = false, const float* pts = nullptr) {
     if (!h) return fail(LCM_ERR_INVALID_ARG, "bad argument");
     int rc = check_rows(n); if (rc) return rc;
-    if (n > 0 && !rows) return fail(LCM_ERR_INVALID_ARG, "NULL buffer");
+    if (n > 0 && (!rows || (with_pts && !pts))) return fail(LCM_ERR_INVALID_ARG, "NULL buffer");
     L2Store& d = h->l2db;
     if (d.rows.size() >= 0x7FFFFFFFull) return fail(LCM_ERR_CAPACITY, "too many stored frames");
     rc = set_device(h); if (rc) return rc;
@@ -502,11 +543,13 @@ int l2_db_append_impl(lcm_handle* h, const uint8_t* rows, int n, int* slot) {
     }
     std::vector<uint32_t> meta;
     rc = store_put(h, rows, n, first, meta); if (rc) return rc;
+    if (with_pts) { rc = store_put_pts(h, pts, n, first); if (rc) return rc; }
     const uint2 entry = make_uint2((uint32_t)first, (uint32_t)n);
     HIP_TRY(hipMemcpyAsync(d.d_frames + n_slots, &entry, sizeof(entry), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));     // the caller's rows (pageable) have been consumed
     d.rows.push_back(n);
     d.tile0.push_back((uint32_t)(first + tiles_of(n)));
+    d.has_pts.push_back(with_pts ? 1 : 0);
     if (slot) *slot = (int)n_slots;
     return LCM_OK;
 }
@@ -536,6 +579,22 @@ int l2_db_truncate_impl(lcm_handle* h, int n_frames) {
     if ((size_t)n_frames > d.rows.size()) return fail(LCM_ERR_INVALID_ARG, "cannot truncate %zu frames to %d", d.rows.size(), n_frames);
     d.rows.resize((size_t)n_frames);
     d.tile0.resize((size_t)n_frames + 1);
+    d.has_pts.resize((size_t)n_frames);
+    return LCM_OK;
+}
+
+int l2_db_read_kp_impl(lcm_handle* h, int slot, float* out, int cap_rows) {
+    if (!h) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+    int rc = check_slot(h, slot); if (rc) return rc;
+    const L2Store& d = h->l2db;
+    if (!d.has_pts[(size_t)slot]) return fail(LCM_ERR_INVALID_ARG, "slot %d was stored without points", slot);
+    const int n = d.rows[(size_t)slot];
+    if (cap_rows < n) return fail(LCM_ERR_CAPACITY, "slot %d holds %d rows but the buffer %d", slot, n, cap_rows);
+    if (n == 0) return LCM_OK;
+    if (!out) return fail(LCM_ERR_INVALID_ARG, "NULL buffer");
+    rc = set_device(h); if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, d.d_pts + (size_t)d.tile0[(size_t)slot] * TILE, (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return LCM_OK;
 }
 
@@ -543,7 +602,8 @@ int l2_db_info_impl(lcm_handle* h, lcm_l2_db_info* out) {
     if (!h || !out) return fail(LCM_ERR_INVALID_ARG, "bad argument");
     const L2Store& d = h->l2db;
     *out = lcm_l2_db_info{(int32_t)d.rows.size(), 0, d.tile0.back(), d.cap_tiles,
-                          d.cap_tiles * (2 * (uint64_t)lcm::L2_TILE_BYTES + TILE * sizeof(uint32_t)) + d.d_frames_cap * sizeof(uint2),
+                          d.cap_tiles * (2 * (uint64_t)lcm::L2_TILE_BYTES + TILE * sizeof(uint32_t) + (d.d_pts ? TILE * sizeof(uint2) : 0)) +
+                              d.d_frames_cap * sizeof(uint2),
                           d.last_table_bytes};
     return LCM_OK;
 }
@@ -708,6 +768,165 @@ int l2_db_detect_loops_impl(lcm_handle* h, int curr, const uint8_t* query, int n
     return rc;
 }
 
+// ---- lists and keypoints from the device (lcm_l2_emit.hip) -------------------------------------------------------------------
+static_assert(sizeof(size_t) == sizeof(uint64_t) && sizeof(lcm_dmatch) == sizeof(uint4) && sizeof(lcm_point_pair) == sizeof(uint4), "record sizes");
+
+// The lists of job_of.size() pairs over the store's tile space: rows[f] rows at tile d.tile0[f] (f == size: a host query
+// staged in the free tail); live[job_of[p]] = pair p, -1 when a side is empty.  Score, fold, rescan, then the ratio test, the
+// ordered compaction and the gather on the device; offsets (8 bytes per pair) come back first and decide about `cap`, then
+// only the records do.  pts == NULL: no point pairs.
+int store_lists(lcm_handle* h, const int* rows, int n_frames, const std::vector<L2Pair>& live, const std::vector<int>& job_of,
+                double ratio, lcm_dmatch* out, lcm_point_pair* pts, size_t cap, size_t* offsets) {
+    const size_t n_pairs = job_of.size();
+    if (live.empty()) {
+        std::fill(offsets, offsets + n_pairs + 1, (size_t)0);
+        return LCM_OK;
+    }
+    L2Store& d = h->l2db;
+    if (pts && !d.d_pts) return fail(LCM_ERR_INVALID_ARG, "the store holds no points");
+    const uint32_t* fin = nullptr;
+    std::vector<size_t> row0;
+    L2OnDevice dv;
+    int rc = l2_run(h, nullptr, rows, n_frames, live, &fin, row0, &d, &dv); if (rc) return rc;
+    const size_t P = live.size(), total_rows = row0[P];
+
+    // [first block of the first live pair at or after p, p <= n_pairs | survivors per block, + their total]
+    std::vector<uint32_t> pair_block(n_pairs + 1);
+    uint32_t next = (uint32_t)dv.n_blocks;
+    pair_block[n_pairs] = next;
+    for (size_t p = n_pairs; p-- > 0;) {
+        if (job_of[p] >= 0) next = dv.first_block[(size_t)job_of[p]];
+        pair_block[p] = next;
+    }
+    auto& s = h->l2;
+    rc = ensure_dev(s.d_blocks, s.d_blocks_n, n_pairs + 1 + dv.n_blocks + 1); if (rc) return rc;
+    rc = ensure_dev(s.d_offsets, s.d_offsets_n, n_pairs + 1); if (rc) return rc;
+    uint32_t* d_blocks = s.d_blocks + n_pairs + 1;
+    HIP_TRY(hipMemcpyAsync(s.d_blocks, pair_block.data(), (n_pairs + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    lcm::L2EmitArgs ea{s.d_fin, dv.d_jobs, d_blocks, nullptr, nullptr, nullptr, ratio, 0, 0};
+    uint32_t lim = 1;
+    hipError_t e = lcm::grid_y_limit(&lim);
+    if (e != hipSuccess) return fail(LCM_ERR_HIP, "grid limit: %s", hipGetErrorString(e));
+    const uint32_t slices = (uint32_t)((P + lim - 1) / lim);
+    HIP_TRY(hipEventRecord(h->ev_aux_start, h->stream));
+    e = lcm::launch_l2_emit_count(ea, (uint32_t)P, (uint32_t)dv.max_nq, h->stream);
+    if (e == hipSuccess) e = lcm::launch_block_scan(d_blocks, (uint32_t)dv.n_blocks, d_blocks + dv.n_blocks, h->stream);
+    if (e == hipSuccess) e = lcm::launch_l2_emit_offsets(d_blocks, s.d_blocks, s.d_offsets, (uint32_t)(n_pairs + 1), h->stream);
+    if (e != hipSuccess) return fail(LCM_ERR_HIP, "list count kernels: launch failed: %s", hipGetErrorString(e));
+    h->info.launches += slices + 2;
+    HIP_TRY(hipMemcpyAsync(offsets, s.d_offsets, (n_pairs + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));       // also: l2_run's tables and pair_block (pageable) have been consumed
+    const size_t total = offsets[n_pairs];
+    h->info.algo_bytes += 2 * total_rows * 16 + (n_pairs + 1) * 8 + total * (pts ? 48 : 16);
+    if (total > total_rows) return fail(LCM_ERR_HIP, "list count %zu exceeds the %zu query rows", total, total_rows);
+    if (total > (out ? cap : 0)) {
+        HIP_TRY(hipEventRecord(h->ev_aux_stop, h->stream));
+        h->aux_pending = true;
+        return fail(LCM_ERR_CAPACITY, "%zu matches but the buffer holds %zu records", total, out ? cap : (size_t)0);
+    }
+    if (total) {
+        rc = ensure_dev(s.d_rec, s.d_rec_n, total); if (rc) return rc;
+        if (pts) { rc = ensure_dev(s.d_rec_pts, s.d_rec_pts_n, total); if (rc) return rc; }
+        ea.out = s.d_rec; ea.n_out = (uint32_t)total;
+        if (pts) { ea.pts = d.d_pts; ea.out_pts = s.d_rec_pts; }
+        e = lcm::launch_l2_emit(ea, (uint32_t)P, (uint32_t)dv.max_nq, h->stream);
+        if (e != hipSuccess) return fail(LCM_ERR_HIP, "list kernel launch failed: %s", hipGetErrorString(e));
+        h->info.launches += slices;
+    }
+    HIP_TRY(hipEventRecord(h->ev_aux_stop, h->stream));
+    h->aux_pending = true;
+    if (total) {
+        HIP_TRY(hipMemcpyAsync(out, s.d_rec, total * sizeof(uint4), hipMemcpyDeviceToHost, h->stream));
+        if (pts) HIP_TRY(hipMemcpyAsync(pts, s.d_rec_pts, total * sizeof(uint4), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    return LCM_OK;
+}
+
+// `slot` is named by a list call that wants points: its rows must have theirs
+int check_slot_pts(const L2Store& d, int slot) {
+    if (d.rows[(size_t)slot] > 0 && !d.has_pts[(size_t)slot]) return fail(LCM_ERR_INVALID_ARG, "slot %d was stored without points", slot);
+    return LCM_OK;
+}
+
+int l2_db_match_points_impl(lcm_handle* h, const lcm_pair_ref* slots, int n_pairs, double ratio, lcm_dmatch* out, lcm_point_pair* pts,
+                            size_t cap, size_t* offsets) {
+    if (!h || n_pairs < 0 || !offsets || (n_pairs > 0 && !slots)) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+    offsets[0] = 0;
+    int rc = check_knn(h, ratio); if (rc) return rc;
+    const L2Store& d = h->l2db;
+    const int S = (int)d.rows.size();
+    std::vector<L2Pair> live;
+    std::vector<int> job_of((size_t)n_pairs, -1);
+    for (int p = 0; p < n_pairs; ++p) {
+        const int q = slots[p].query_frame_id, t = slots[p].train_frame_id;
+        if (q < 0 || q >= S || t < 0 || t >= S) return fail(LCM_ERR_INVALID_ARG, "pair %d: position outside [0, %d)", p, S);
+        if (pts) {
+            rc = check_slot_pts(d, q); if (rc) return rc;
+            rc = check_slot_pts(d, t); if (rc) return rc;
+        }
+        if (d.rows[(size_t)q] == 0 || d.rows[(size_t)t] == 0) continue;
+        job_of[(size_t)p] = (int)live.size();
+        live.push_back(L2Pair{q, t});
+    }
+    return store_lists(h, d.rows.data(), S, live, job_of, ratio, out, pts, cap, offsets);
+}
+
+int l2_db_detect_loops_points_impl(lcm_handle* h, int curr, const uint8_t* query, const float* query_pts, int nq, const uint8_t* skip,
+                                   int loop_gap, const lcm_ratio_loop_params* rp_in, lcm_loop_candidate* cands, size_t cand_cap,
+                                   size_t* n_cands, size_t* n_pairs_out, lcm_dmatch* out, lcm_point_pair* pts, size_t cap, size_t* offsets) {
+    if (!offsets) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+    lcm_ratio_loop_params rp;
+    int rc = store_search_args(h, loop_gap, rp_in, n_cands, n_pairs_out, &rp); if (rc) return rc;
+    offsets[0] = 0;
+    L2Store& d = h->l2db;
+    const int S = (int)d.rows.size();
+    StoreCurr c{curr, 0, 0, 0};
+    std::vector<uint32_t> meta;
+    if (query) {
+        rc = check_rows(nq); if (rc) return rc;
+        if (pts && !query_pts) return fail(LCM_ERR_INVALID_ARG, "point pairs are wanted but the query has no points");
+    } else {
+        rc = check_slot(h, curr); if (rc) return rc;
+        if (pts) { rc = check_slot_pts(d, curr); if (rc) return rc; }
+        c.q_tile = d.tile0[(size_t)curr]; c.q_rows = d.rows[(size_t)curr];
+    }
+    // everything from the staging on: whatever happens, the caller's rows and points have been consumed on return
+    auto body = [&]() -> int {
+        if (query) {
+            const size_t first = d.tile0.back();
+            int r = store_reserve(h, std::max<size_t>(first + tiles_of(nq), 1)); if (r) return r;
+            r = store_put(h, query, nq, first, meta); if (r) return r;
+            if (query_pts) { r = store_put_pts(h, query_pts, nq, first); if (r) return r; }
+            c.q_tile = (uint32_t)first; c.q_rows = nq;
+        }
+        c.last_past = (int)std::max<long long>((long long)curr - loop_gap, -1);
+        std::vector<StoreCurr> currs;
+        if (c.q_rows >= rp.min_rows) currs.push_back(c);                        // :1382
+        int r = store_search(h, currs, skip, rp, cands, cand_cap, n_cands, n_pairs_out); if (r) return r;
+        // the candidates' lists: query = position S of the extended row table (the staged rows) or the slot `curr`
+        std::vector<int> rows_ext(d.rows);
+        rows_ext.push_back(query ? nq : 0);
+        const int qpos = query ? S : curr;
+        std::vector<L2Pair> live;
+        std::vector<int> job_of(*n_cands, -1);
+        for (size_t k = 0; k < *n_cands; ++k) {
+            const int t = cands[k].matched_frame_id;
+            if (pts) { r = check_slot_pts(d, t); if (r) return r; }
+            if (rows_ext[(size_t)qpos] == 0 || d.rows[(size_t)t] == 0) continue;
+            job_of[k] = (int)live.size();
+            live.push_back(L2Pair{qpos, t});
+        }
+        return store_lists(h, rows_ext.data(), S + 1, live, job_of, rp.ratio, out, pts, cap, offsets);
+    };
+    rc = body();
+    if (query && nq > 0) {
+        const hipError_t e = hipStreamSynchronize(h->stream);                   // a path that launched nothing has not waited
+        if (e != hipSuccess && rc == LCM_OK) return fail(LCM_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
+    }
+    return rc;
+}
+
 int l2_ratio_test_device_impl(lcm_handle* h, const uint32_t* d1, const uint32_t* d2, size_t n, double ratio, uint8_t* pass) {
     if (!h || (n > 0 && (!d1 || !d2 || !pass))) return fail(LCM_ERR_INVALID_ARG, "bad argument");
     if (std::isnan(ratio) || ratio < 0.0) return fail(LCM_ERR_INVALID_ARG, "ratio must be a number >= 0");
@@ -803,6 +1022,24 @@ int lcm_l2_db_loop_search(lcm_handle* h, const uint8_t* skip, int loop_gap, cons
 int lcm_l2_db_detect_loops(lcm_handle* h, int curr, const uint8_t* query, int nq, const uint8_t* skip, int loop_gap,
                            const lcm_ratio_loop_params* rp, lcm_loop_candidate* out, size_t cap, size_t* n_out, size_t* n_pairs_out) {
     return guarded([&] { return l2_db_detect_loops_impl(h, curr, query, nq, skip, loop_gap, rp, out, cap, n_out, n_pairs_out); });
+}
+int lcm_l2_db_append_kp(lcm_handle* h, const uint8_t* rows, const float* pts, int n, int* slot) {
+    return guarded([&] { return l2_db_append_impl(h, rows, n, slot, true, pts); });
+}
+int lcm_l2_db_read_kp(lcm_handle* h, int slot, float* out, int cap_rows) {
+    return guarded([&] { return l2_db_read_kp_impl(h, slot, out, cap_rows); });
+}
+int lcm_l2_db_match_points(lcm_handle* h, const lcm_pair_ref* slots, int n_pairs, double ratio, lcm_dmatch* out, lcm_point_pair* pts,
+                           size_t cap, size_t* offsets) {
+    return guarded([&] { return l2_db_match_points_impl(h, slots, n_pairs, ratio, out, pts, cap, offsets); });
+}
+int lcm_l2_db_detect_loops_points(lcm_handle* h, int curr, const uint8_t* query, const float* query_pts, int nq, const uint8_t* skip,
+                                  int loop_gap, const lcm_ratio_loop_params* rp, lcm_loop_candidate* cands, size_t cand_cap,
+                                  size_t* n_cands, size_t* n_pairs_out, lcm_dmatch* out, lcm_point_pair* pts, size_t cap, size_t* offsets) {
+    return guarded([&] {
+        return l2_db_detect_loops_points_impl(h, curr, query, query_pts, nq, skip, loop_gap, rp, cands, cand_cap, n_cands, n_pairs_out, out,
+                                              pts, cap, offsets);
+    });
 }
 int lcm_l2_ratio_test_device(lcm_handle* h, const uint32_t* d1, const uint32_t* d2, size_t n, double ratio, uint8_t* pass) {
     return guarded([&] { return l2_ratio_test_device_impl(h, d1, d2, n, ratio, pass); });

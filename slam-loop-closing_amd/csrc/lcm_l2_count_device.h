@@ -1,7 +1,7 @@
 // lcm_l2_count_device.h — the body of the ratio-test count on SIFT rows, shared by the two kernels that run it:
 // k_l2_count (lcm_l2_count.hip: the item comes from a host-built table) and k_l2_count_store (lcm_l2_store.hip: the
 // workgroup derives its item from the store's tables).  The verdict, the roots and the top-2 walk exist here, once.
-// Included by those two files only.
+// lcm_l2_emit.hip (the survivors' lists) takes the verdict and the root from here too.  Included by those three files only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
