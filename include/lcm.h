@@ -439,6 +439,71 @@ LCM_API extern int lcm_l2_db_detect_loops_points(lcm_handle* h, int curr, const 
                                                  lcm_loop_candidate* cands, size_t cand_cap, size_t* n_cands, size_t* n_pairs_out,
                                                  lcm_dmatch* out, lcm_point_pair* pts, size_t cap, size_t* offsets);
 
+/* ---- loop verification on the device: essential-matrix RANSAC over the correspondences ---------------------------------- */
+/* src/main.cpp:1395-1403: E = findEssentialMat(ptsCurr, ptsPast, K, RANSAC, 0.999, 1.0, mask), inliers = countNonZero(mask),
+ * and the verdict `inliers > 200 && inliers / matches > 0.6`.  This is NOT OpenCV's estimator bit for bit: the minimal solver
+ * is the linear EIGHT-point method (not the five-point one: it is degenerate on an all-planar scene) and the number of
+ * hypotheses is FIXED (`iters`, not adaptive).  Every step is defined here and deterministic (lcm_epi_device.h):
+ *   normalisation  (u, v) -> x = ((double)u - cx) / fx, y = ((double)v - cy) / fy; query x1 = (a, b, 1), train x2 = (c, d, 1),
+ *                  x2^T E x1 = 0 (curr = query = points1, the reference's argument order)
+ *   threshold      t = threshold / ((fx + fy) / 2), t2 = t * t
+ *   error          E row-major e0..e8: p0 = e0 a + e1 b + e2, p1 = e3 a + e4 b + e5, p2 = e6 a + e7 b + e8,
+ *                  q0 = e0 c + e3 d + e6, q1 = e1 c + e4 d + e7, num = c p0 + d p1 + p2, den = p0^2 + p1^2 + q0^2 + q1^2;
+ *                  in double, every product and sum rounded on its own, sums left to right
+ *   inlier         den > 0 && num * num <= t2 * den
+ *   sampling       hypothesis `it` of pair `p` draws 8 distinct records by Floyd's algorithm from a 32-bit counter hash of
+ *                  (seed, p, it, draw); p is the pair's position in the call
+ *   solver         null vector of the 8 x 9 system by elimination with full pivoting, singular values forced to (1, 1, 0);
+ *                  a rank-deficient sample gives the all-zero matrix, which has no inlier
+ *   selection      the largest inlier count over the `iters` hypotheses, among equals the lowest hypothesis
+ * A pair with fewer than 8 records: status LCM_EPI_TOO_FEW, zero E, no inliers, an all-zero mask.  A pair holds at most
+ * 65 535 records (LCM_ERR_CAPACITY).  Ordered on the handle's stream and finished on return. */
+typedef struct lcm_epi_params {
+    double   fx, fy, cx, cy;    /* the camera matrix K; the defaults leave it zero: fx <= 0 or fy <= 0 is LCM_ERR_INVALID_ARG */
+    double   threshold;         /* pixels, 1.0 */
+    double   min_ratio;         /* 0.6:  lcm_epi_loop_test */
+    int32_t  iters;             /* 1024: hypotheses per pair, a multiple of 64 in [64, 65536] */
+    int32_t  min_inliers;       /* 200:  lcm_epi_loop_test */
+    uint32_t seed;              /* 0 */
+    uint32_t reserved;
+} lcm_epi_params;               /* 64 bytes */
+typedef enum lcm_epi_status { LCM_EPI_OK = 0, LCM_EPI_TOO_FEW = 1 } lcm_epi_status;
+typedef struct lcm_epi_result {
+    double  E[9];               /* row-major, singular values (1, 1, 0); all zero when no hypothesis had an inlier */
+    int32_t n_points, n_inliers, best_iter, status;
+} lcm_epi_result;               /* 88 bytes */
+LCM_API void lcm_epi_params_default(lcm_epi_params* p);
+/* Host only: n_inliers > min_inliers && (double)n_inliers / n_points > min_ratio, both strict (:1403); 0 for a NULL. */
+LCM_API int  lcm_epi_loop_test(const lcm_epi_result* r, const lcm_epi_params* ep);
+/* The RANSAC over host point lists in the layout lcm_l2_db_match_points returns: pair p owns pts[offsets[p] .. offsets[p + 1]),
+ * offsets[0] == 0.  results: n_pairs records; mask (may be NULL): offsets[n_pairs] bytes, 1 = inlier of the pair's E.
+ * lcm_last_launch_info: kernel_ms is the three kernels'. */
+LCM_API int  lcm_epi_verify_pairs(lcm_handle* h, const lcm_point_pair* pts, const size_t* offsets, int n_pairs,
+                                  const lcm_epi_params* ep, lcm_epi_result* results, uint8_t* mask);
+/* Test and plug-in seams.  lcm_epi_hypotheses: what the solver kernel makes of ONE pair of n records standing at position
+ * pair_index of a call: samples = iters x 8 indices (-1 when n < 8), E = iters x 9 doubles.  lcm_epi_score_models: the scoring
+ * kernel's inlier count of each of n_models (1 .. 65536) caller-supplied matrices E = n_models x 9 over n records. */
+LCM_API int  lcm_epi_hypotheses(lcm_handle* h, const lcm_point_pair* pts, int n, uint32_t pair_index, const lcm_epi_params* ep,
+                                int32_t* samples, double* E);
+LCM_API int  lcm_epi_score_models(lcm_handle* h, const lcm_point_pair* pts, int n, const double* E, int n_models,
+                                  const lcm_epi_params* ep, int32_t* counts);
+/* lcm_l2_db_match_points followed by the RANSAC on the point records the list kernel has just written, before anything is
+ * copied back: out, pts (required here) and offsets are byte for byte lcm_l2_db_match_points's, results / mask as
+ * lcm_epi_verify_pairs's on those points.  `cap` too small: as lcm_l2_db_match_points, and neither results nor mask are written.
+ * lcm_last_launch_info: as after lcm_l2_db_match_points, the three kernels added to launches and to aux_kernel_ms. */
+LCM_API int  lcm_epi_db_verify_pairs(lcm_handle* h, const lcm_pair_ref* slots, int n_pairs, double ratio, const lcm_epi_params* ep,
+                                     lcm_epi_result* results, lcm_dmatch* out, lcm_point_pair* pts, uint8_t* mask, size_t cap,
+                                     size_t* offsets);
+/* lcm_l2_db_detect_loops_points plus the verification: one iteration of the reference's outer loop through the first two clauses
+ * of :1403.  Candidates, lists, point pairs and offsets are unchanged; results[c] (cand_cap records) and the mask bytes
+ * [offsets[c], offsets[c + 1]) belong to candidate c, whose sampler is seeded with c.  The third clause (> globalMaxInliers)
+ * and recoverPose stay with the caller. */
+LCM_API int  lcm_epi_db_detect_loops(lcm_handle* h, int curr, const uint8_t* query, const float* query_pts, int nq,
+                                     const uint8_t* skip, int loop_gap, const struct lcm_ratio_loop_params* rp,
+                                     const lcm_epi_params* ep, lcm_loop_candidate* cands, size_t cand_cap, size_t* n_cands,
+                                     size_t* n_pairs_out, lcm_epi_result* results, lcm_dmatch* out, lcm_point_pair* pts,
+                                     uint8_t* mask, size_t cap, size_t* offsets);
+
 /* ---- loop search against the stored database --------------------------------------------------------- */
 /* Score `query` (id query_frame_id) against every stored frame with query_frame_id - id >= min_gap, ascending
  * slot order.  out_scores / out_frame_ids need room for lcm_db_size() records. */

@@ -60,6 +60,22 @@ class PointPair(C.Structure):
     _fields_ = [("qx", C.c_float), ("qy", C.c_float), ("tx", C.c_float), ("ty", C.c_float)]
 
 
+class EpiParams(C.Structure):
+    """lcm_epi_params: the camera matrix and the settings of the essential-matrix RANSAC (64 bytes)."""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("threshold", C.c_double),
+                ("min_ratio", C.c_double), ("iters", C.c_int32), ("min_inliers", C.c_int32), ("seed", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class EpiResult(C.Structure):
+    """lcm_epi_result: a pair's winning essential matrix (row-major) and its inlier count (88 bytes)."""
+    _fields_ = [("E", C.c_double * 9), ("n_points", C.c_int32), ("n_inliers", C.c_int32), ("best_iter", C.c_int32),
+                ("status", C.c_int32)]
+
+
+EPI_OK, EPI_TOO_FEW = 0, 1               # lcm_epi_status
+
+
 class L2DbInfo(C.Structure):
     """lcm_l2_db_info: the SIFT keyframe store's occupancy and the table bytes of its last search."""
     _fields_ = [("frames", C.c_int32), ("reserved_", C.c_int32), ("tiles_used", C.c_uint64), ("tiles_reserved", C.c_uint64),
@@ -94,6 +110,9 @@ DMATCH_DTYPE = np.dtype([("query_idx", "<i4"), ("train_idx", "<i4"), ("img_idx",
 CANDIDATE_DTYPE = np.dtype([("current_frame_id", "<i4"), ("matched_frame_id", "<i4"), ("num_matches", "<i4"),
                             ("_pad", "<i4"), ("similarity_score", "<f8")])
 L2_SCORE_DTYPE = np.dtype([("good_count", "<u4"), ("min_dist_sq", "<u4")])      # lcm_l2_score
+EPI_RESULT_DTYPE = np.dtype([("E", "<f8", (9,)), ("n_points", "<i4"), ("n_inliers", "<i4"), ("best_iter", "<i4"),
+                             ("status", "<i4")])                              # lcm_epi_result
+assert EPI_RESULT_DTYPE.itemsize == C.sizeof(EpiResult) == 88 and C.sizeof(EpiParams) == 64
 assert SCORE_DTYPE.itemsize == C.sizeof(Score) == 8
 assert L2_SCORE_DTYPE.itemsize == 8
 assert C.sizeof(PointPair) == 16          # returned as float32[n, 4]: (qx, qy, tx, ty)
@@ -163,6 +182,15 @@ _SIGNATURES = {
     "lcm_l2_db_match_points": (C.c_int, [_vp, _vp, C.c_int, C.c_double, _vp, _vp, C.c_size_t, _vp]),
     "lcm_l2_db_detect_loops_points": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(RatioLoopParams), _vp,
                                                  C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _vp, _vp, C.c_size_t, _vp]),
+    "lcm_epi_params_default": (None, [C.POINTER(EpiParams)]),
+    "lcm_epi_loop_test": (C.c_int, [C.POINTER(EpiResult), C.POINTER(EpiParams)]),
+    "lcm_epi_verify_pairs": (C.c_int, [_vp, _vp, _vp, C.c_int, C.POINTER(EpiParams), _vp, _vp]),
+    "lcm_epi_hypotheses": (C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.POINTER(EpiParams), _vp, _vp]),
+    "lcm_epi_score_models": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(EpiParams), _vp]),
+    "lcm_epi_db_verify_pairs": (C.c_int, [_vp, _vp, C.c_int, C.c_double, C.POINTER(EpiParams), _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "lcm_epi_db_detect_loops": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(RatioLoopParams),
+                                           C.POINTER(EpiParams), _vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                           _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "lcm_query_scores": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _i32p]),
     "lcm_query_submit": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _i32p]),
     "lcm_query_collect": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i32p]),
@@ -264,6 +292,36 @@ def default_params() -> Params:
 def default_ratio_loop_params() -> RatioLoopParams:
     p = RatioLoopParams()
     load_library().lcm_ratio_loop_params_default(C.byref(p))
+    return p
+
+
+def default_epi_params(fx: float = 0.0, fy: float = 0.0, cx: float = 0.0, cy: float = 0.0, **over) -> EpiParams:
+    """lcm_epi_params_default (threshold 1.0, iters 1024, min_inliers 200, min_ratio 0.6, seed 0) with the camera matrix and
+    any other field given by name.  The defaults leave K zero: a call with fx <= 0 or fy <= 0 is refused."""
+    p = EpiParams()
+    load_library().lcm_epi_params_default(C.byref(p))
+    p.fx, p.fy, p.cx, p.cy = fx, fy, cx, cy
+    for k, v in over.items():
+        if k not in ("threshold", "min_ratio", "iters", "min_inliers", "seed"):
+            raise TypeError(f"lcm_epi_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def epi_loop_test(result, ep: EpiParams) -> bool:
+    """lcm_epi_loop_test (host only): n_inliers > min_inliers and n_inliers / n_points > min_ratio, both strict.  result: an
+    EPI_RESULT_DTYPE record or an EpiResult."""
+    if not isinstance(result, EpiResult):
+        r = EpiResult()
+        r.n_points, r.n_inliers, r.best_iter, r.status = (int(result[k]) for k in ("n_points", "n_inliers", "best_iter", "status"))
+        result = r
+    return bool(load_library().lcm_epi_loop_test(C.byref(result), C.byref(ep)))
+
+
+def _point_pairs(pts) -> np.ndarray:
+    p = np.ascontiguousarray(pts, dtype=np.float32)
+    if p.ndim != 2 or p.shape[1] != 4:
+        raise ValueError(f"point pairs must be (n, 4) float32 (qx, qy, tx, ty), got {p.shape}")
     return p
 
 
@@ -794,6 +852,94 @@ class Matcher:
                                                        offs.ctypes.data_as(_vp)))
         total = int(offs[n.value])
         return cands[: n.value], npairs.value, out[:total], (pts[:total] if points else None), offs[: n.value + 1]
+
+    # -- loop verification: essential-matrix RANSAC on the device (lcm_epi_*) --
+    def epi_verify_pairs(self, pts, offsets, ep: EpiParams, want_mask: bool = True):
+        """The RANSAC over host point pairs float32[total, 4] in the offsets layout of l2_db_match_points:
+        (EPI_RESULT_DTYPE[n_pairs], uint8[total] inlier mask or None)."""
+        offs = np.ascontiguousarray(offsets, np.uintp)
+        n = len(offs) - 1
+        p = _point_pairs(pts)
+        assert n >= 0 and len(p) >= (int(offs[n]) if n >= 0 else 0)
+        res = np.zeros(max(n, 1), EPI_RESULT_DTYPE)
+        mask = np.zeros(max(int(offs[n]), 1), np.uint8) if want_mask else None
+        _check(self._lib.lcm_epi_verify_pairs(self._h, _ptr(p), offs.ctypes.data_as(_vp), n, C.byref(ep), res.ctypes.data_as(_vp),
+                                              None if mask is None else mask.ctypes.data_as(_vp)))
+        return res[:n], (None if mask is None else mask[: int(offs[n])])
+
+    def epi_hypotheses(self, pts, pair_index: int, ep: EpiParams):
+        """What the solver kernel makes of one pair standing at position pair_index of a call: (int32[iters, 8] sample
+        indices, float64[iters, 9] essential matrices, row-major)."""
+        p = _point_pairs(pts)
+        samples = np.zeros((ep.iters, 8), np.int32)
+        E = np.zeros((ep.iters, 9), np.float64)
+        _check(self._lib.lcm_epi_hypotheses(self._h, _ptr(p), len(p), pair_index, C.byref(ep), samples.ctypes.data_as(_vp),
+                                            E.ctypes.data_as(_vp)))
+        return samples, E
+
+    def epi_score_models(self, pts, E, ep: EpiParams) -> np.ndarray:
+        """The scoring kernel's inlier count of every matrix of E float64[n_models, 9] over the point pairs: int32[n_models]."""
+        p = _point_pairs(pts)
+        e = np.ascontiguousarray(E, np.float64).reshape(-1, 9)
+        counts = np.zeros(len(e), np.int32)
+        _check(self._lib.lcm_epi_score_models(self._h, _ptr(p), len(p), _ptr(e), len(e), C.byref(ep), counts.ctypes.data_as(_vp)))
+        return counts
+
+    def epi_db_verify_pairs(self, pairs: Sequence[Tuple[int, int]], ratio: float, ep: EpiParams, cap: Optional[int] = None,
+                            out: Optional[np.ndarray] = None, pts: Optional[np.ndarray] = None,
+                            results: Optional[np.ndarray] = None, mask: Optional[np.ndarray] = None):
+        """l2_db_match_points followed by the RANSAC on the device's own point records: (EPI_RESULT_DTYPE[n], DMATCH_DTYPE[total],
+        float32[total, 4], uint8[total] mask, offsets[n + 1]).  out / pts / results / mask: the caller's buffers."""
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n = pr.shape[0]
+        if cap is None:
+            if out is not None:
+                cap = len(out)
+            else:
+                size = self.l2_db_size()
+                cap = sum(self.l2_db_rows(int(q)) for q in pr[:, 0] if 0 <= q < size)
+        out = np.zeros(max(cap, 1), DMATCH_DTYPE) if out is None else out
+        pts = np.zeros((max(cap, 1), 4), np.float32) if pts is None else pts
+        results = np.zeros(max(n, 1), EPI_RESULT_DTYPE) if results is None else results
+        mask = np.zeros(max(cap, 1), np.uint8) if mask is None else mask
+        assert out.dtype == DMATCH_DTYPE and out.flags["C_CONTIGUOUS"] and len(out) >= cap
+        assert pts.dtype == np.float32 and pts.flags["C_CONTIGUOUS"] and pts.shape[1:] == (4,) and len(pts) >= cap
+        assert results.dtype == EPI_RESULT_DTYPE and len(results) >= n and mask.dtype == np.uint8 and len(mask) >= cap
+        offs = np.zeros(n + 1, np.uintp)
+        self.last_offsets = offs
+        _check(self._lib.lcm_epi_db_verify_pairs(self._h, _ptr(pr), n, ratio, C.byref(ep), results.ctypes.data_as(_vp),
+                                                 out.ctypes.data_as(_vp), pts.ctypes.data_as(_vp), mask.ctypes.data_as(_vp), cap,
+                                                 offs.ctypes.data_as(_vp)))
+        total = int(offs[n])
+        return results[:n], out[:total], pts[:total], mask[:total], offs
+
+    def epi_db_detect_loops(self, curr: int, loop_gap: int, ep: EpiParams, query=None, query_pts=None, skip=None,
+                            ratio: Optional[float] = None, min_rows: Optional[int] = None, min_matches: Optional[int] = None,
+                            cand_cap: Optional[int] = None, cap: Optional[int] = None):
+        """l2_db_detect_loops_points plus the verification of every candidate: (candidates, pairs scored, EPI_RESULT_DTYPE
+        [n_candidates], DMATCH_DTYPE[total], float32[total, 4], uint8[total] mask, offsets[n_candidates + 1])."""
+        rpp, _rp, sk, cand_cap, cands = self._l2_db_search_args(skip, ratio, min_rows, min_matches, cand_cap, None)
+        q = None if query is None else _sift_rows(query)
+        nq = 0 if q is None else q.shape[0]
+        qp = None if q is None else (q if q.size else np.zeros((1, SIFT_BYTES), np.uint8)).ctypes.data_as(_vp)
+        kp = None if (q is None or query_pts is None) else self._kp(query_pts, nq)
+        kpp = None if kp is None else (kp if kp.size else np.zeros((1, 2), np.float32)).ctypes.data_as(_vp)
+        if cap is None:
+            rows_q = nq if q is not None else (self.l2_db_rows(curr) if 0 <= curr < self.l2_db_size() else 0)
+            cap = rows_q * max(min(cand_cap, self.l2_db_size()), 1)
+        out = np.zeros(max(cap, 1), DMATCH_DTYPE)
+        pts = np.zeros((max(cap, 1), 4), np.float32)
+        mask = np.zeros(max(cap, 1), np.uint8)
+        results = np.zeros(max(cand_cap, 1), EPI_RESULT_DTYPE)
+        offs = np.zeros(cand_cap + 1, np.uintp)
+        n, npairs = C.c_size_t(0), C.c_size_t(0)
+        self.last_offsets, self.last_n_cands = offs, n
+        _check(self._lib.lcm_epi_db_detect_loops(self._h, curr, qp, kpp, nq, _ptr(sk), loop_gap, rpp, C.byref(ep),
+                                                 cands.ctypes.data_as(_vp), cand_cap, C.byref(n), C.byref(npairs),
+                                                 results.ctypes.data_as(_vp), out.ctypes.data_as(_vp), pts.ctypes.data_as(_vp),
+                                                 mask.ctypes.data_as(_vp), cap, offs.ctypes.data_as(_vp)))
+        total = int(offs[n.value])
+        return cands[: n.value], npairs.value, results[: n.value], out[:total], pts[:total], mask[:total], offs[: n.value + 1]
 
     # -- loop search -------------------------------------------------------------------------------
     def query_scores(self, query, query_frame_id: int) -> Tuple[np.ndarray, np.ndarray]:

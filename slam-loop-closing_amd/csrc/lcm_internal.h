@@ -7,6 +7,7 @@
 //   lcm_ratio.cpp      bulk / online loop search scored with Lowe's ratio test
 //   lcm_l2.cpp         pair mode on 128-byte SIFT rows under L2 (knnMatch(k = 2) + ratio test), ratio-test counts per pair,
 //                      the SIFT keyframe store (lcm_l2_db_*)
+//   lcm_epi.cpp        essential-matrix RANSAC over the loop candidates' correspondences (lcm_epi_*)
 // Not installed; the public surface is include/lcm.h.
 #pragma once
 #include "../../include/lcm.h"
@@ -263,6 +264,18 @@ struct lcm_handle {
         std::vector<int> rows;
         size_t last_table_bytes = 0;
     } l2db;
+    // essential-matrix RANSAC (lcm_epi.cpp): a host call's points and offsets, the hypotheses (8 indices + 9 doubles each),
+    // the per-pair best key, the seam's counts, the result records and the mask
+    struct EpiScratch {
+        uint4* d_pts = nullptr;       size_t d_pts_n = 0;
+        uint64_t* d_off = nullptr;    size_t d_off_n = 0;
+        int32_t* d_samples = nullptr; size_t d_samples_n = 0;
+        double* d_E = nullptr;        size_t d_E_n = 0;
+        uint32_t* d_best = nullptr;   size_t d_best_n = 0;
+        uint32_t* d_counts = nullptr; size_t d_counts_n = 0;
+        lcm_epi_result* d_res = nullptr; size_t d_res_n = 0;
+        uint8_t* d_mask = nullptr;    size_t d_mask_n = 0;
+    } epi;
     lcm_launch_info info{};
     bool info_pending = false;
 };
@@ -386,6 +399,16 @@ int stored_src(lcm_handle* h, int frame_id, RowSrc* out, int* n_kp);    // devic
 // frames train_ids; else the stored pairs): job_of[p] = pair p's job, -1 when a side is empty.
 int batch_jobs(lcm_handle* h, const uint8_t* q_host, int nq_host, const lcm_pair_ref* pairs, const int32_t* train_ids,
                int n_pairs, std::vector<PairJob>& jobs, std::vector<int>& job_of, size_t* stage_bytes);
+// ---- lcm_epi.cpp: the RANSAC behind lcm_epi_*; lcm_l2.cpp runs it on the list kernel's point records
+// ep checked (LCM_ERR_INVALID_ARG and the message otherwise)
+int epi_params_checked(const lcm_epi_params* ep);
+// Enqueues k_epi_solve, k_epi_score and k_epi_mask on h's stream over n_pairs pairs whose records d_pts[d_off[p] .. d_off[p + 1])
+// are on the device (max_n = the longest pair, total = d_off[n_pairs]); results -> h->epi.d_res, mask -> h->epi.d_mask.
+// *launches = kernel launches made.  No host wait.
+int epi_enqueue(lcm_handle* h, const uint4* d_pts, const uint64_t* d_off, size_t n_pairs, uint32_t max_n, size_t total,
+                const lcm_epi_params& ep, uint32_t* launches);
+// Copies of the last epi_enqueue's records to the host, enqueued (the caller waits); mask may be NULL
+int epi_download(lcm_handle* h, size_t n_pairs, size_t total, lcm_epi_result* results, uint8_t* mask);
 }  // namespace lcm
 
 namespace {

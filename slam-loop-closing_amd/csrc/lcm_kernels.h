@@ -271,6 +271,31 @@ hipError_t launch_l2_emit(const L2EmitArgs& a, uint32_t n_jobs, uint32_t max_nq,
 // n_blocks (the total) past the last one
 hipError_t launch_l2_emit_offsets(const uint32_t* blocks, const uint32_t* pair_block, uint64_t* offsets, uint32_t n, hipStream_t st);
 
+// ---- essential-matrix RANSAC over the pairs' point lists (lcm_epi.hip): src/main.cpp:1395-1403 -------------------------
+// Pair p of the call owns the records pts[offsets[p] .. offsets[p + 1]) = {qx, qy, tx, ty} as float bits (k_l2_emit's point
+// records, or a caller's lcm_point_pair array) and `iters` hypotheses: samples[(p * iters + it) * 8 ..], E[(p * iters + it) *
+// 9 ..].  best[p] = max over the hypotheses of (inliers << 16 | 0xFFFF - it), zeroed before launch_epi_score.  The sampler
+// is seeded with pair_seed0 + p.  counts (optional): every hypothesis's inlier count.  results / mask: k_epi_mask's output,
+// one lcm_epi_result per pair and one byte per record.
+struct EpiArgs {
+    const uint4*    pts;
+    const uint64_t* offsets;     // n_pairs + 1
+    int32_t*        samples;
+    double*         E;
+    uint32_t*       best;
+    uint32_t*       counts;      // NULL: not wanted
+    void*           results;     // EpiResult (lcm_epi_device.h) per pair
+    uint8_t*        mask;
+    double          fx, fy, cx, cy, t2;
+    uint32_t        iters;       // multiple of 64
+    uint32_t        seed;
+    uint32_t        pair_seed0;
+    uint32_t        pair_base;   // set by the launchers: pair of blockIdx.y == 0 (slices of grid_y_limit() pairs)
+};
+hipError_t launch_epi_solve(const EpiArgs& a, uint32_t n_pairs, hipStream_t st);
+hipError_t launch_epi_score(const EpiArgs& a, uint32_t n_pairs, hipStream_t st);
+hipError_t launch_epi_mask(const EpiArgs& a, uint32_t n_pairs, uint32_t max_n, hipStream_t st);
+
 // ---- bulk / online loop search scored with Lowe's ratio test (lcm_ratio.hip): src/main.cpp:1375-1388 -------------------
 // One workgroup = one WorkItem (or an implicit run of stored slots for ONE query frame, as ScoreArgs' implicit items):
 // per pair, good_count = number of query rows with best < ratio * second (knnMatch(k = 2) order, the second smallest

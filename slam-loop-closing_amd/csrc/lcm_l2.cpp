@@ -5,9 +5,12 @@
 // double.  The loop search's form (lcm_score_pairs_ratio_l2, lcm_loop_search_ratio_l2) wants the survivor COUNT per pair
 // only: lcm_l2_count.hip scores a pair's whole train matrix in one workgroup per query chunk and decides on the device, so
 // 8 bytes per pair come back.  The SIFT keyframe store (lcm_l2_db_*) keeps uploaded and packed matrices on the device and
-// searches them from tables that grow with the frames (lcm_l2_store.hip).  Part of liblcm_hip.so's host side (C ABI in include/lcm.h); shared state and helpers:
+// searches them from tables that grow with the frames (lcm_l2_store.hip); its list calls can hand the point records straight to
+// the essential-matrix RANSAC (lcm_epi_db_*: store_lists enqueues lcm_epi.cpp's kernels).  Part of liblcm_hip.so's host side (C ABI in include/lcm.h); shared state and helpers:
 // lcm_internal.h.
 #include "lcm_internal.h"
+
+#include "lcm_epi_host.h"
 
 #include <cmath>
 #include <limits>
@@ -775,11 +778,16 @@ static_assert(sizeof(size_t) == sizeof(uint64_t) && sizeof(lcm_dmatch) == sizeof
 // staged in the free tail); live[job_of[p]] = pair p, -1 when a side is empty.  Score, fold, rescan, then the ratio test, the
 // ordered compaction and the gather on the device; offsets (8 bytes per pair) come back first and decide about `cap`, then
 // only the records do.  pts == NULL: no point pairs.
+// epi != NULL (with pts): the essential-matrix RANSAC (lcm_epi.hip) runs on the point records as soon as k_l2_emit has written
+// them, pair p of the call seeded with p; its kernels count into `launches` and into the aux events' span.
+struct EpiWanted { const lcm_epi_params* ep; lcm_epi_result* results; uint8_t* mask; };
+
 int store_lists(lcm_handle* h, const int* rows, int n_frames, const std::vector<L2Pair>& live, const std::vector<int>& job_of,
-                double ratio, lcm_dmatch* out, lcm_point_pair* pts, size_t cap, size_t* offsets) {
+                double ratio, lcm_dmatch* out, lcm_point_pair* pts, size_t cap, size_t* offsets, const EpiWanted* epi = nullptr) {
     const size_t n_pairs = job_of.size();
     if (live.empty()) {
         std::fill(offsets, offsets + n_pairs + 1, (size_t)0);
+        if (epi) lcm::epi_empty_results(epi->results, n_pairs);
         return LCM_OK;
     }
     L2Store& d = h->l2db;
@@ -833,13 +841,20 @@ int store_lists(lcm_handle* h, const int* rows, int n_frames, const std::vector<
         if (e != hipSuccess) return fail(LCM_ERR_HIP, "list kernel launch failed: %s", hipGetErrorString(e));
         h->info.launches += slices;
     }
+    if (epi) {                                      // a pair's records are at most its query rows: they fit the packed key
+        uint32_t max_n = 0, launches = 0;
+        for (size_t p = 0; p < n_pairs; ++p) max_n = std::max(max_n, (uint32_t)(offsets[p + 1] - offsets[p]));
+        rc = lcm::epi_enqueue(h, s.d_rec_pts, s.d_offsets, n_pairs, max_n, total, *epi->ep, &launches); if (rc) return rc;
+        h->info.launches += launches;
+    }
     HIP_TRY(hipEventRecord(h->ev_aux_stop, h->stream));
     h->aux_pending = true;
     if (total) {
         HIP_TRY(hipMemcpyAsync(out, s.d_rec, total * sizeof(uint4), hipMemcpyDeviceToHost, h->stream));
         if (pts) HIP_TRY(hipMemcpyAsync(pts, s.d_rec_pts, total * sizeof(uint4), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
     }
+    if (epi) { rc = lcm::epi_download(h, n_pairs, total, epi->results, epi->mask); if (rc) return rc; }
+    if (total || epi) HIP_TRY(hipStreamSynchronize(h->stream));
     return LCM_OK;
 }
 
@@ -850,8 +865,12 @@ int check_slot_pts(const L2Store& d, int slot) {
 }
 
 int l2_db_match_points_impl(lcm_handle* h, const lcm_pair_ref* slots, int n_pairs, double ratio, lcm_dmatch* out, lcm_point_pair* pts,
-                            size_t cap, size_t* offsets) {
+                            size_t cap, size_t* offsets, const EpiWanted* epi = nullptr) {
     if (!h || n_pairs < 0 || !offsets || (n_pairs > 0 && !slots)) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+    if (epi) {
+        const int rc = lcm::epi_params_checked(epi->ep); if (rc) return rc;
+        if (!pts || (n_pairs > 0 && !epi->results)) return fail(LCM_ERR_INVALID_ARG, "the verification needs pts and results");
+    }
     offsets[0] = 0;
     int rc = check_knn(h, ratio); if (rc) return rc;
     const L2Store& d = h->l2db;
@@ -869,13 +888,19 @@ int l2_db_match_points_impl(lcm_handle* h, const lcm_pair_ref* slots, int n_pair
         job_of[(size_t)p] = (int)live.size();
         live.push_back(L2Pair{q, t});
     }
-    return store_lists(h, d.rows.data(), S, live, job_of, ratio, out, pts, cap, offsets);
+    return store_lists(h, d.rows.data(), S, live, job_of, ratio, out, pts, cap, offsets, epi);
 }
 
 int l2_db_detect_loops_points_impl(lcm_handle* h, int curr, const uint8_t* query, const float* query_pts, int nq, const uint8_t* skip,
                                    int loop_gap, const lcm_ratio_loop_params* rp_in, lcm_loop_candidate* cands, size_t cand_cap,
-                                   size_t* n_cands, size_t* n_pairs_out, lcm_dmatch* out, lcm_point_pair* pts, size_t cap, size_t* offsets) {
+                                   size_t* n_cands, size_t* n_pairs_out, lcm_dmatch* out, lcm_point_pair* pts, size_t cap, size_t* offsets,
+                                   const EpiWanted* epi = nullptr) {
     if (!offsets) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+    if (epi) {
+        if (!h) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+        const int r = lcm::epi_params_checked(epi->ep); if (r) return r;
+        if (!pts || (cand_cap > 0 && !epi->results)) return fail(LCM_ERR_INVALID_ARG, "the verification needs pts and results");
+    }
     lcm_ratio_loop_params rp;
     int rc = store_search_args(h, loop_gap, rp_in, n_cands, n_pairs_out, &rp); if (rc) return rc;
     offsets[0] = 0;
@@ -917,7 +942,7 @@ int l2_db_detect_loops_points_impl(lcm_handle* h, int curr, const uint8_t* query
             job_of[k] = (int)live.size();
             live.push_back(L2Pair{qpos, t});
         }
-        return store_lists(h, rows_ext.data(), S + 1, live, job_of, rp.ratio, out, pts, cap, offsets);
+        return store_lists(h, rows_ext.data(), S + 1, live, job_of, rp.ratio, out, pts, cap, offsets, epi);
     };
     rc = body();
     if (query && nq > 0) {
@@ -1039,6 +1064,23 @@ int lcm_l2_db_detect_loops_points(lcm_handle* h, int curr, const uint8_t* query,
     return guarded([&] {
         return l2_db_detect_loops_points_impl(h, curr, query, query_pts, nq, skip, loop_gap, rp, cands, cand_cap, n_cands, n_pairs_out, out,
                                               pts, cap, offsets);
+    });
+}
+int lcm_epi_db_verify_pairs(lcm_handle* h, const lcm_pair_ref* slots, int n_pairs, double ratio, const lcm_epi_params* ep,
+                            lcm_epi_result* results, lcm_dmatch* out, lcm_point_pair* pts, uint8_t* mask, size_t cap, size_t* offsets) {
+    return guarded([&] {
+        const EpiWanted w{ep, results, mask};
+        return l2_db_match_points_impl(h, slots, n_pairs, ratio, out, pts, cap, offsets, &w);
+    });
+}
+int lcm_epi_db_detect_loops(lcm_handle* h, int curr, const uint8_t* query, const float* query_pts, int nq, const uint8_t* skip,
+                            int loop_gap, const lcm_ratio_loop_params* rp, const lcm_epi_params* ep, lcm_loop_candidate* cands,
+                            size_t cand_cap, size_t* n_cands, size_t* n_pairs_out, lcm_epi_result* results, lcm_dmatch* out,
+                            lcm_point_pair* pts, uint8_t* mask, size_t cap, size_t* offsets) {
+    return guarded([&] {
+        const EpiWanted w{ep, results, mask};
+        return l2_db_detect_loops_points_impl(h, curr, query, query_pts, nq, skip, loop_gap, rp, cands, cand_cap, n_cands, n_pairs_out, out,
+                                              pts, cap, offsets, &w);
     });
 }
 int lcm_l2_ratio_test_device(lcm_handle* h, const uint32_t* d1, const uint32_t* d2, size_t n, double ratio, uint8_t* pass) {
