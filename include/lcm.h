@@ -497,12 +497,84 @@ LCM_API int  lcm_epi_db_verify_pairs(lcm_handle* h, const lcm_pair_ref* slots, i
 /* lcm_l2_db_detect_loops_points plus the verification: one iteration of the reference's outer loop through the first two clauses
  * of :1403.  Candidates, lists, point pairs and offsets are unchanged; results[c] (cand_cap records) and the mask bytes
  * [offsets[c], offsets[c + 1]) belong to candidate c, whose sampler is seeded with c.  The third clause (> globalMaxInliers)
- * and recoverPose stay with the caller. */
+ * and recoverPose (:1405-1421) are lcm_pose_db_detect_loops's, below. */
 LCM_API int  lcm_epi_db_detect_loops(lcm_handle* h, int curr, const uint8_t* query, const float* query_pts, int nq,
                                      const uint8_t* skip, int loop_gap, const struct lcm_ratio_loop_params* rp,
                                      const lcm_epi_params* ep, lcm_loop_candidate* cands, size_t cand_cap, size_t* n_cands,
                                      size_t* n_pairs_out, lcm_epi_result* results, lcm_dmatch* out, lcm_point_pair* pts,
                                      uint8_t* mask, size_t cap, size_t* offsets);
+
+/* ---- the loop's relative pose on the device, and the best loop ------------------------------------------------------------ */
+/* src/main.cpp:1405-1421: poseInliers = recoverPose(E, ptsCurr, ptsPast, K, R_loop, t_loop, mask), the verdict
+ * `poseInliers > 100`, and the globalBest* update.  This is NOT cv::recoverPose bit for bit (OpenCV decomposes by SVD and
+ * triangulates by a 4 x 4 DLT per point).  Every step here is +, -, x, / and a square root in double, every product and sum
+ * rounded on its own, sums left to right (lcm_pose_device.h):
+ *   convention   the RANSAC's: query x1 = (a, b, 1), train x2 = (c, d, 1), normalised as above; x2^T E x1 = 0, E = [t]x R,
+ *                that is X2 = R X1 + t with |t| = 1 (the argument order of :1407)
+ *   scale        e = E * sqrt(2 / |E|^2_F): the RANSAC's E and a caller's take one path.  A caller's E must be essential; it
+ *                is not projected.  |E|^2_F zero, NaN or outside the range in which that scale is finite, or an e without
+ *                two independent columns: LCM_POSE_NO_MODEL (so after LCM_EPI_TOO_FEW and after a pair without an inlier)
+ *   translation  c0 = col1 x col2, c1 = col2 x col0, c2 = col0 x col1 of e; the one with the largest squared norm, first of
+ *                equals: t^ = c_k / sqrt(|c_k|^2).  No sign canonicalisation
+ *   rotations    C = the cofactor matrix of e (row 0 = row1 x row2, row 1 = row2 x row0, row 2 = row0 x row1), M = [t^]x e:
+ *                Ra = C - M, Rb = C + M
+ *   hypotheses   k = 0 .. 3: R = (k & 1) ? Rb : Ra, t = (k & 2) ? -t^ : t^
+ *   depth test   u = R x1, v = x2; uu = u.u, vv = v.v, uv = u.v, ut = u.t, vt = v.t; D = uu vv - uv uv, n1 = uv vt - vv ut,
+ *                n2 = uu vt - uv ut (n1 / D, n2 / D: the least-squares depths of the two rays).  In front of both cameras:
+ *                D > 0 && n1 > 0 && n2 > 0 && n1 < max_depth D && n2 < max_depth D.  No division
+ *   records      only those whose input mask byte is non-zero take part (no mask: all)
+ *   selection    the largest of the four counts, among equals the lowest k; mask_out = 1 where a record took part and passes
+ *                under the chosen k; n_good = their number = counts[choice]: poseInliers of :1407
+ * t has the sign that puts the points in front.  R, t inherit the quality of E: the eight-point E is a minimal-sample estimate. */
+typedef struct lcm_pose_params {
+    double  max_depth;          /* 50.0: OpenCV's distanceThresh, in units of the baseline; <= 0 or NaN is LCM_ERR_INVALID_ARG */
+    int32_t min_pose_inliers;   /* 100:  lcm_pose_loop_test */
+    int32_t reserved[5];
+} lcm_pose_params;              /* 32 bytes */
+typedef enum lcm_pose_status { LCM_POSE_OK = 0, LCM_POSE_NO_MODEL = 1 } lcm_pose_status;
+typedef struct lcm_pose_result {
+    double  R[9];               /* row-major */
+    double  t[3];               /* unit */
+    int32_t counts[4];          /* records in front of both cameras under each hypothesis */
+    int32_t n_used, n_good, choice, status;      /* records that took part; counts[choice]; k */
+} lcm_pose_result;              /* 128 bytes.  LCM_POSE_NO_MODEL: all zero but choice = -1 and status, and an all-zero mask */
+LCM_API void lcm_pose_params_default(lcm_pose_params* p);
+/* Host only: lcm_epi_loop_test(er, ep) && pr->status == LCM_POSE_OK && pr->n_good > pp->min_pose_inliers, strict (:1409).
+ * pp == NULL: the defaults (in every call of the family); 0 for any other NULL. */
+LCM_API int  lcm_pose_loop_test(const lcm_epi_result* er, const lcm_pose_result* pr, const lcm_epi_params* ep,
+                                const lcm_pose_params* pp);
+/* Host only: *best = the index of the candidate with the largest n_inliers > floor_inliers among those of the n that pass
+ * lcm_pose_loop_test, among equals the lowest index; -1 when there is none.  Walked in (curr, past) order this is the
+ * reference's globalBest* update (a candidate that fails the pose test does not raise the maximum there either): the caller
+ * carries floor_inliers = the best n_inliers so far from keyframe to keyframe, starting at -1. */
+LCM_API int  lcm_pose_best(const lcm_epi_result* epi_results, const lcm_pose_result* pose_results, int n, const lcm_epi_params* ep,
+                           const lcm_pose_params* pp, int floor_inliers, int* best);
+/* Point lists and matrices verified elsewhere, in lcm_epi_verify_pairs's layout: pair p owns pts[offsets[p] .. offsets[p + 1])
+ * and E[9 p .. 9 p + 9).  mask_in (may be NULL: every record) and mask_out (may be NULL): offsets[n_pairs] bytes.  ep supplies
+ * K only.  Refusals as lcm_epi_verify_pairs's.  lcm_last_launch_info: kernel_ms is the kernel's. */
+LCM_API int  lcm_pose_recover_pairs(lcm_handle* h, const lcm_point_pair* pts, const size_t* offsets, int n_pairs, const double* E,
+                                    const uint8_t* mask_in, const lcm_epi_params* ep, const lcm_pose_params* pp,
+                                    lcm_pose_result* results, uint8_t* mask_out);
+/* Test seam: the decomposition alone, on the device.  Model m of E = n_models x 9 gives R4[36 m ..] = 4 x 9 and
+ * t4[12 m ..] = 4 x 3 (hypothesis k at 9 k and 3 k) and status[m]; all zero for LCM_POSE_NO_MODEL. */
+LCM_API int  lcm_pose_candidates(lcm_handle* h, const double* E, int n_models, double* R4, double* t4, int32_t* status);
+/* lcm_epi_db_verify_pairs followed by the pose recovery on the records, matrices and mask the RANSAC has just written, before
+ * anything is copied back: everything lcm_epi_db_verify_pairs returns is returned byte for byte; pose_results (n_pairs) and
+ * pose_mask (`cap` bytes, may be NULL) as lcm_pose_recover_pairs's on the returned points, E and mask.  `cap` too small: as
+ * there, and nothing new is written either.  lcm_last_launch_info: one more launch, inside aux_kernel_ms. */
+LCM_API int  lcm_pose_db_verify_pairs(lcm_handle* h, const lcm_pair_ref* slots, int n_pairs, double ratio, const lcm_epi_params* ep,
+                                      const lcm_pose_params* pp, lcm_epi_result* results, lcm_pose_result* pose_results,
+                                      lcm_dmatch* out, lcm_point_pair* pts, uint8_t* mask, uint8_t* pose_mask, size_t cap,
+                                      size_t* offsets);
+/* lcm_epi_db_detect_loops plus the pose recovery and the choice: one iteration of the reference's outer loop through :1421.
+ * pose_results: cand_cap records.  *best = lcm_pose_best over the call's candidates with floor_inliers (-1 before the first
+ * keyframe; afterwards the n_inliers of the best loop so far), or -1; it is written only when the call succeeds. */
+LCM_API int  lcm_pose_db_detect_loops(lcm_handle* h, int curr, const uint8_t* query, const float* query_pts, int nq,
+                                      const uint8_t* skip, int loop_gap, const struct lcm_ratio_loop_params* rp,
+                                      const lcm_epi_params* ep, const lcm_pose_params* pp, lcm_loop_candidate* cands,
+                                      size_t cand_cap, size_t* n_cands, size_t* n_pairs_out, lcm_epi_result* results,
+                                      lcm_pose_result* pose_results, lcm_dmatch* out, lcm_point_pair* pts, uint8_t* mask,
+                                      uint8_t* pose_mask, size_t cap, size_t* offsets, int floor_inliers, int* best);
 
 /* ---- loop search against the stored database --------------------------------------------------------- */
 /* Score `query` (id query_frame_id) against every stored frame with query_frame_id - id >= min_gap, ascending

@@ -76,6 +76,21 @@ class EpiResult(C.Structure):
 EPI_OK, EPI_TOO_FEW = 0, 1               # lcm_epi_status
 
 
+class PoseParams(C.Structure):
+    """lcm_pose_params: the far limit of the depth test (in baselines) and the pose verdict's limit (32 bytes)."""
+    _fields_ = [("max_depth", C.c_double), ("min_pose_inliers", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+class PoseResult(C.Structure):
+    """lcm_pose_result: a pair's relative pose X2 = R X1 + t (R row-major, |t| = 1), the four hypotheses' counts, the records
+    that took part, those in front of both cameras under the chosen hypothesis, that hypothesis, the status (128 bytes)."""
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("counts", C.c_int32 * 4), ("n_used", C.c_int32),
+                ("n_good", C.c_int32), ("choice", C.c_int32), ("status", C.c_int32)]
+
+
+POSE_OK, POSE_NO_MODEL = 0, 1            # lcm_pose_status
+
+
 class L2DbInfo(C.Structure):
     """lcm_l2_db_info: the SIFT keyframe store's occupancy and the table bytes of its last search."""
     _fields_ = [("frames", C.c_int32), ("reserved_", C.c_int32), ("tiles_used", C.c_uint64), ("tiles_reserved", C.c_uint64),
@@ -113,6 +128,9 @@ L2_SCORE_DTYPE = np.dtype([("good_count", "<u4"), ("min_dist_sq", "<u4")])      
 EPI_RESULT_DTYPE = np.dtype([("E", "<f8", (9,)), ("n_points", "<i4"), ("n_inliers", "<i4"), ("best_iter", "<i4"),
                              ("status", "<i4")])                              # lcm_epi_result
 assert EPI_RESULT_DTYPE.itemsize == C.sizeof(EpiResult) == 88 and C.sizeof(EpiParams) == 64
+POSE_RESULT_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("counts", "<i4", (4,)), ("n_used", "<i4"), ("n_good", "<i4"),
+                              ("choice", "<i4"), ("status", "<i4")])          # lcm_pose_result
+assert POSE_RESULT_DTYPE.itemsize == C.sizeof(PoseResult) == 128 and C.sizeof(PoseParams) == 32
 assert SCORE_DTYPE.itemsize == C.sizeof(Score) == 8
 assert L2_SCORE_DTYPE.itemsize == 8
 assert C.sizeof(PointPair) == 16          # returned as float32[n, 4]: (qx, qy, tx, ty)
@@ -191,6 +209,16 @@ _SIGNATURES = {
     "lcm_epi_db_detect_loops": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(RatioLoopParams),
                                            C.POINTER(EpiParams), _vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                            _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "lcm_pose_params_default": (None, [C.POINTER(PoseParams)]),
+    "lcm_pose_loop_test": (C.c_int, [C.POINTER(EpiResult), C.POINTER(PoseResult), C.POINTER(EpiParams), C.POINTER(PoseParams)]),
+    "lcm_pose_best": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(EpiParams), C.POINTER(PoseParams), C.c_int, _i32p]),
+    "lcm_pose_recover_pairs": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, C.POINTER(EpiParams), C.POINTER(PoseParams), _vp, _vp]),
+    "lcm_pose_candidates": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "lcm_pose_db_verify_pairs": (C.c_int, [_vp, _vp, C.c_int, C.c_double, C.POINTER(EpiParams), C.POINTER(PoseParams), _vp, _vp, _vp,
+                                            _vp, _vp, _vp, C.c_size_t, _vp]),
+    "lcm_pose_db_detect_loops": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(RatioLoopParams),
+                                            C.POINTER(EpiParams), C.POINTER(PoseParams), _vp, C.c_size_t, C.POINTER(C.c_size_t),
+                                            C.POINTER(C.c_size_t), _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_int, _i32p]),
     "lcm_query_scores": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _i32p]),
     "lcm_query_submit": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _i32p]),
     "lcm_query_collect": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i32p]),
@@ -316,6 +344,48 @@ def epi_loop_test(result, ep: EpiParams) -> bool:
         r.n_points, r.n_inliers, r.best_iter, r.status = (int(result[k]) for k in ("n_points", "n_inliers", "best_iter", "status"))
         result = r
     return bool(load_library().lcm_epi_loop_test(C.byref(result), C.byref(ep)))
+
+
+def default_pose_params(**over) -> PoseParams:
+    """lcm_pose_params_default (max_depth 50.0, min_pose_inliers 100) with any field given by name."""
+    p = PoseParams()
+    load_library().lcm_pose_params_default(C.byref(p))
+    for k, v in over.items():
+        if k not in ("max_depth", "min_pose_inliers"):
+            raise TypeError(f"lcm_pose_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def _pose_result(result) -> PoseResult:
+    if isinstance(result, PoseResult):
+        return result
+    r = PoseResult()
+    r.n_used, r.n_good, r.choice, r.status = (int(result[k]) for k in ("n_used", "n_good", "choice", "status"))
+    return r
+
+
+def pose_loop_test(epi_result, pose_result, ep: EpiParams, pp: Optional[PoseParams] = None) -> bool:
+    """lcm_pose_loop_test (host only): epi_loop_test and n_good > min_pose_inliers, strict.  The results: records of
+    EPI_RESULT_DTYPE / POSE_RESULT_DTYPE or the ctypes structures."""
+    if not isinstance(epi_result, EpiResult):
+        r = EpiResult()
+        r.n_points, r.n_inliers, r.best_iter, r.status = (int(epi_result[k]) for k in ("n_points", "n_inliers", "best_iter", "status"))
+        epi_result = r
+    pr = _pose_result(pose_result)
+    return bool(load_library().lcm_pose_loop_test(C.byref(epi_result), C.byref(pr), C.byref(ep), None if pp is None else C.byref(pp)))
+
+
+def pose_best(epi_results, pose_results, ep: EpiParams, pp: Optional[PoseParams] = None, floor_inliers: int = -1) -> int:
+    """lcm_pose_best (host only) over EPI_RESULT_DTYPE[n] and POSE_RESULT_DTYPE[n]: the index of the best loop among the
+    candidates with more than floor_inliers inliers, or -1."""
+    er = np.ascontiguousarray(epi_results, EPI_RESULT_DTYPE)
+    pr = np.ascontiguousarray(pose_results, POSE_RESULT_DTYPE)
+    assert len(er) == len(pr)
+    best = C.c_int32(-2)
+    _check(load_library().lcm_pose_best(er.ctypes.data_as(_vp), pr.ctypes.data_as(_vp), len(er), C.byref(ep),
+                                        None if pp is None else C.byref(pp), floor_inliers, C.byref(best)))
+    return best.value
 
 
 def _point_pairs(pts) -> np.ndarray:
@@ -940,6 +1010,110 @@ class Matcher:
                                                  mask.ctypes.data_as(_vp), cap, offs.ctypes.data_as(_vp)))
         total = int(offs[n.value])
         return cands[: n.value], npairs.value, results[: n.value], out[:total], pts[:total], mask[:total], offs[: n.value + 1]
+
+    # -- the loop's relative pose on the device and the best loop (lcm_pose_*) --
+    def pose_recover_pairs(self, pts, offsets, E, ep: EpiParams, pp: Optional[PoseParams] = None, mask_in=None,
+                           want_mask: bool = True):
+        """recoverPose over host point pairs float32[total, 4] in the offsets layout of l2_db_match_points, pair p under
+        E[p] (float64[n_pairs, 9], row-major); mask_in uint8[total] or None = every record.  ep supplies K only.
+        (POSE_RESULT_DTYPE[n_pairs], uint8[total] mask of the records in front of both cameras, or None)."""
+        offs = np.ascontiguousarray(offsets, np.uintp)
+        n = len(offs) - 1
+        p = _point_pairs(pts)
+        e = np.ascontiguousarray(E, np.float64).reshape(-1, 9)
+        total = int(offs[n]) if n >= 0 else 0
+        assert n >= 0 and len(p) >= total and len(e) >= n
+        mi = None if mask_in is None else np.ascontiguousarray(mask_in, np.uint8)
+        assert mi is None or len(mi) >= total
+        res = np.zeros(max(n, 1), POSE_RESULT_DTYPE)
+        mask = np.zeros(max(total, 1), np.uint8) if want_mask else None
+        _check(self._lib.lcm_pose_recover_pairs(self._h, _ptr(p), offs.ctypes.data_as(_vp), n, _ptr(e), None if mi is None else _ptr(mi),
+                                                C.byref(ep), None if pp is None else C.byref(pp), res.ctypes.data_as(_vp),
+                                                None if mask is None else mask.ctypes.data_as(_vp)))
+        return res[:n], (None if mask is None else mask[:total])
+
+    def pose_candidates(self, E):
+        """The kernel's decomposition alone: (float64[n, 4, 9] rotations, float64[n, 4, 3] translations, int32[n] status) of
+        the matrices E float64[n, 9]; hypothesis k = (Ra, t), (Rb, t), (Ra, -t), (Rb, -t)."""
+        e = np.ascontiguousarray(E, np.float64).reshape(-1, 9)
+        n = len(e)
+        R4, t4, status = np.zeros((max(n, 1), 4, 9)), np.zeros((max(n, 1), 4, 3)), np.zeros(max(n, 1), np.int32)
+        _check(self._lib.lcm_pose_candidates(self._h, _ptr(e), n, R4.ctypes.data_as(_vp), t4.ctypes.data_as(_vp), status.ctypes.data_as(_vp)))
+        return R4[:n], t4[:n], status[:n]
+
+    def pose_db_verify_pairs(self, pairs: Sequence[Tuple[int, int]], ratio: float, ep: EpiParams, pp: Optional[PoseParams] = None,
+                             cap: Optional[int] = None, out: Optional[np.ndarray] = None, pts: Optional[np.ndarray] = None,
+                             results: Optional[np.ndarray] = None, mask: Optional[np.ndarray] = None,
+                             pose_results: Optional[np.ndarray] = None, pose_mask: Optional[np.ndarray] = None):
+        """epi_db_verify_pairs followed by the pose recovery on the device's own records, matrices and mask:
+        (EPI_RESULT_DTYPE[n], POSE_RESULT_DTYPE[n], DMATCH_DTYPE[total], float32[total, 4], uint8[total] inlier mask,
+        uint8[total] pose mask, offsets[n + 1]).  out / pts / results / mask / pose_results / pose_mask: the caller's buffers."""
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n = pr.shape[0]
+        if cap is None:
+            if out is not None:
+                cap = len(out)
+            else:
+                size = self.l2_db_size()
+                cap = sum(self.l2_db_rows(int(q)) for q in pr[:, 0] if 0 <= q < size)
+        out = np.zeros(max(cap, 1), DMATCH_DTYPE) if out is None else out
+        pts = np.zeros((max(cap, 1), 4), np.float32) if pts is None else pts
+        results = np.zeros(max(n, 1), EPI_RESULT_DTYPE) if results is None else results
+        mask = np.zeros(max(cap, 1), np.uint8) if mask is None else mask
+        pose_results = np.zeros(max(n, 1), POSE_RESULT_DTYPE) if pose_results is None else pose_results
+        pose_mask = np.zeros(max(cap, 1), np.uint8) if pose_mask is None else pose_mask
+        assert out.dtype == DMATCH_DTYPE and out.flags["C_CONTIGUOUS"] and len(out) >= cap
+        assert pts.dtype == np.float32 and pts.flags["C_CONTIGUOUS"] and pts.shape[1:] == (4,) and len(pts) >= cap
+        assert results.dtype == EPI_RESULT_DTYPE and len(results) >= n and mask.dtype == np.uint8 and len(mask) >= cap
+        assert pose_results.dtype == POSE_RESULT_DTYPE and len(pose_results) >= n and pose_mask.dtype == np.uint8 and len(pose_mask) >= cap
+        offs = np.zeros(n + 1, np.uintp)
+        self.last_offsets = offs
+        _check(self._lib.lcm_pose_db_verify_pairs(self._h, _ptr(pr), n, ratio, C.byref(ep), None if pp is None else C.byref(pp),
+                                                  results.ctypes.data_as(_vp), pose_results.ctypes.data_as(_vp),
+                                                  out.ctypes.data_as(_vp), pts.ctypes.data_as(_vp), mask.ctypes.data_as(_vp),
+                                                  pose_mask.ctypes.data_as(_vp), cap, offs.ctypes.data_as(_vp)))
+        total = int(offs[n])
+        return results[:n], pose_results[:n], out[:total], pts[:total], mask[:total], pose_mask[:total], offs
+
+    def pose_db_detect_loops(self, curr: int, loop_gap: int, ep: EpiParams, pp: Optional[PoseParams] = None, floor_inliers: int = -1,
+                             query=None, query_pts=None, skip=None, ratio: Optional[float] = None, min_rows: Optional[int] = None,
+                             min_matches: Optional[int] = None, cand_cap: Optional[int] = None, cap: Optional[int] = None):
+        """epi_db_detect_loops plus the pose recovery of every candidate and the choice of the best loop: (candidates, pairs
+        scored, EPI_RESULT_DTYPE[n_candidates], POSE_RESULT_DTYPE[n_candidates], DMATCH_DTYPE[total], float32[total, 4],
+        uint8[total] inlier mask, uint8[total] pose mask, offsets[n_candidates + 1], best).  best: the index of the candidate
+        the reference's globalBest* update ends at when it starts from floor_inliers, or -1."""
+        rpp, _rp, sk, cand_cap, cands = self._l2_db_search_args(skip, ratio, min_rows, min_matches, cand_cap, None)
+        q = None if query is None else _sift_rows(query)
+        nq = 0 if q is None else q.shape[0]
+        qp = None if q is None else (q if q.size else np.zeros((1, SIFT_BYTES), np.uint8)).ctypes.data_as(_vp)
+        kp = None if (q is None or query_pts is None) else self._kp(query_pts, nq)
+        kpp = None if kp is None else (kp if kp.size else np.zeros((1, 2), np.float32)).ctypes.data_as(_vp)
+        if cap is None:
+            rows_q = nq if q is not None else (self.l2_db_rows(curr) if 0 <= curr < self.l2_db_size() else 0)
+            cap = rows_q * max(min(cand_cap, self.l2_db_size()), 1)
+        out = np.zeros(max(cap, 1), DMATCH_DTYPE)
+        pts = np.zeros((max(cap, 1), 4), np.float32)
+        mask = np.zeros(max(cap, 1), np.uint8)
+        pose_mask = np.zeros(max(cap, 1), np.uint8)
+        results = np.zeros(max(cand_cap, 1), EPI_RESULT_DTYPE)
+        pose_results = np.zeros(max(cand_cap, 1), POSE_RESULT_DTYPE)
+        offs = np.zeros(cand_cap + 1, np.uintp)
+        n, npairs, best = C.c_size_t(0), C.c_size_t(0), C.c_int32(-1)
+        self.last_offsets, self.last_n_cands = offs, n
+        _check(self._lib.lcm_pose_db_detect_loops(self._h, curr, qp, kpp, nq, _ptr(sk), loop_gap, rpp, C.byref(ep),
+                                                  None if pp is None else C.byref(pp), cands.ctypes.data_as(_vp), cand_cap,
+                                                  C.byref(n), C.byref(npairs), results.ctypes.data_as(_vp),
+                                                  pose_results.ctypes.data_as(_vp), out.ctypes.data_as(_vp), pts.ctypes.data_as(_vp),
+                                                  mask.ctypes.data_as(_vp), pose_mask.ctypes.data_as(_vp), cap,
+                                                  offs.ctypes.data_as(_vp), floor_inliers, C.byref(best)))
+        total = int(offs[n.value])
+        return (cands[: n.value], npairs.value, results[: n.value], pose_results[: n.value], out[:total], pts[:total], mask[:total],
+                pose_mask[:total], offs[: n.value + 1], best.value)
+
+    @staticmethod
+    def pose_best(epi_results, pose_results, ep: EpiParams, pp: Optional[PoseParams] = None, floor_inliers: int = -1) -> int:
+        """lcm_pose_best (host only): see capi.pose_best."""
+        return pose_best(epi_results, pose_results, ep, pp, floor_inliers)
 
     # -- loop search -------------------------------------------------------------------------------
     def query_scores(self, query, query_frame_id: int) -> Tuple[np.ndarray, np.ndarray]:

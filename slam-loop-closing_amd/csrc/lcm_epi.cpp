@@ -61,12 +61,8 @@ int epi_download(lcm_handle* h, size_t n_pairs, size_t total, lcm_epi_result* re
     return LCM_OK;
 }
 
-}  // namespace lcm
-
-namespace {
-
 // A host call's records and offsets -> h->epi.d_pts / d_off, enqueued (the sources are pageable: the caller waits)
-int upload_points(lcm_handle* h, const lcm_point_pair* pts, const size_t* offsets, size_t n_pairs, size_t total) {
+int epi_upload_points(lcm_handle* h, const lcm_point_pair* pts, const size_t* offsets, size_t n_pairs, size_t total) {
     auto& s = h->epi;
     int rc = ensure_dev(s.d_pts, s.d_pts_n, total); if (rc) return rc;
     rc = ensure_dev(s.d_off, s.d_off_n, n_pairs + 1); if (rc) return rc;
@@ -74,6 +70,11 @@ int upload_points(lcm_handle* h, const lcm_point_pair* pts, const size_t* offset
     HIP_TRY(hipMemcpyAsync(s.d_off, offsets, (n_pairs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
     return LCM_OK;
 }
+
+}  // namespace lcm
+
+namespace {
+using lcm::epi_upload_points;
 
 int epi_verify_pairs_impl(lcm_handle* h, const lcm_point_pair* pts, const size_t* offsets, int n_pairs, const lcm_epi_params* ep,
                           lcm_epi_result* results, uint8_t* mask) {
@@ -88,7 +89,7 @@ int epi_verify_pairs_impl(lcm_handle* h, const lcm_point_pair* pts, const size_t
     if (n_pairs == 0) return LCM_OK;
     rc = set_device(h); if (rc) return rc;
     const size_t P = (size_t)n_pairs;
-    rc = upload_points(h, pts, offsets, P, total); if (rc) return rc;
+    rc = epi_upload_points(h, pts, offsets, P, total); if (rc) return rc;
     uint32_t launches = 0;
     HIP_TRY(hipEventRecord(h->ev_start, h->stream));
     rc = lcm::epi_enqueue(h, h->epi.d_pts, h->epi.d_off, P, max_n, total, *ep, &launches); if (rc) return rc;
@@ -116,7 +117,7 @@ int epi_hypotheses_impl(lcm_handle* h, const lcm_point_pair* pts, int n, uint32_
     int rc = seam_pair(h, pts, n, ep); if (rc) return rc;
     if (!samples || !E) return fail(LCM_ERR_INVALID_ARG, "NULL buffer");
     const size_t offsets[2] = {0, (size_t)n}, iters = (size_t)ep->iters;
-    rc = upload_points(h, pts, offsets, 1, (size_t)n); if (rc) return rc;
+    rc = epi_upload_points(h, pts, offsets, 1, (size_t)n); if (rc) return rc;
     rc = lcm::epi_reserve(h, 1, iters, (size_t)n); if (rc) return rc;
     lcm::EpiArgs a = lcm::epi_args(h, h->epi.d_pts, h->epi.d_off, *ep, (uint32_t)iters);
     a.pair_seed0 = pair_index;
@@ -134,7 +135,7 @@ int epi_score_models_impl(lcm_handle* h, const lcm_point_pair* pts, int n, const
     if (n_models < 1 || (uint32_t)n_models > lcm::EPI_MAX_ITERS) return fail(LCM_ERR_INVALID_ARG, "n_models must be in [1, %u]", lcm::EPI_MAX_ITERS);
     if (!E || !counts) return fail(LCM_ERR_INVALID_ARG, "NULL buffer");
     const size_t offsets[2] = {0, (size_t)n}, padded = ((size_t)n_models + 63) / 64 * 64;      // whole waves: the pad scores zero matrices
-    rc = upload_points(h, pts, offsets, 1, (size_t)n); if (rc) return rc;
+    rc = epi_upload_points(h, pts, offsets, 1, (size_t)n); if (rc) return rc;
     rc = lcm::epi_reserve(h, 1, padded, (size_t)n); if (rc) return rc;
     rc = ensure_dev(h->epi.d_counts, h->epi.d_counts_n, padded); if (rc) return rc;
     lcm::EpiArgs a = lcm::epi_args(h, h->epi.d_pts, h->epi.d_off, *ep, (uint32_t)padded);

@@ -8,6 +8,7 @@
 //   lcm_l2.cpp         pair mode on 128-byte SIFT rows under L2 (knnMatch(k = 2) + ratio test), ratio-test counts per pair,
 //                      the SIFT keyframe store (lcm_l2_db_*)
 //   lcm_epi.cpp        essential-matrix RANSAC over the loop candidates' correspondences (lcm_epi_*)
+//   lcm_pose.cpp       relative pose of the verified candidates and the best loop (lcm_pose_*)
 // Not installed; the public surface is include/lcm.h.
 #pragma once
 #include "../../include/lcm.h"
@@ -276,6 +277,15 @@ struct lcm_handle {
         lcm_epi_result* d_res = nullptr; size_t d_res_n = 0;
         uint8_t* d_mask = nullptr;    size_t d_mask_n = 0;
     } epi;
+    // relative-pose recovery (lcm_pose.cpp): a host call's matrices and input mask, the seam's candidates (36 + 12 doubles
+    // per model), the result records and the output mask
+    struct PoseScratch {
+        double* d_E = nullptr;        size_t d_E_n = 0;
+        uint8_t* d_mask_in = nullptr; size_t d_mask_in_n = 0;
+        double* d_cand = nullptr;     size_t d_cand_n = 0;
+        lcm_pose_result* d_res = nullptr; size_t d_res_n = 0;
+        uint8_t* d_mask = nullptr;    size_t d_mask_n = 0;
+    } pose;
     lcm_launch_info info{};
     bool info_pending = false;
 };
@@ -409,6 +419,18 @@ int epi_enqueue(lcm_handle* h, const uint4* d_pts, const uint64_t* d_off, size_t
                 const lcm_epi_params& ep, uint32_t* launches);
 // Copies of the last epi_enqueue's records to the host, enqueued (the caller waits); mask may be NULL
 int epi_download(lcm_handle* h, size_t n_pairs, size_t total, lcm_epi_result* results, uint8_t* mask);
+// A host call's records and offsets -> h->epi.d_pts / d_off, enqueued (the sources are pageable: the caller waits)
+int epi_upload_points(lcm_handle* h, const lcm_point_pair* pts, const size_t* offsets, size_t n_pairs, size_t total);
+// ---- lcm_pose.cpp: the pose recovery behind lcm_pose_*; lcm_l2.cpp runs it on the RANSAC's records
+// pp checked (LCM_ERR_INVALID_ARG and the message otherwise); *out = pp's values, or the defaults for NULL
+int pose_params_checked(const lcm_pose_params* pp, lcm_pose_params* out);
+// Enqueues k_pose_recover on h's stream over n_pairs pairs whose records d_pts[d_off[p] .. d_off[p + 1]) are on the device
+// (total = d_off[n_pairs]), pair p's matrix at d_E[p * e_stride ..], d_mask_in (NULL: all) one byte per record; results ->
+// h->pose.d_res, mask -> h->pose.d_mask.  *launches = kernel launches made.  No host wait.
+int pose_enqueue(lcm_handle* h, const uint4* d_pts, const uint64_t* d_off, size_t n_pairs, size_t total, const double* d_E,
+                 uint32_t e_stride, const uint8_t* d_mask_in, const lcm_epi_params& ep, const lcm_pose_params& pp, uint32_t* launches);
+// Copies of the last pose_enqueue's records to the host, enqueued (the caller waits); mask may be NULL
+int pose_download(lcm_handle* h, size_t n_pairs, size_t total, lcm_pose_result* results, uint8_t* mask);
 }  // namespace lcm
 
 namespace {

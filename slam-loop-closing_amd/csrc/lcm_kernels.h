@@ -296,6 +296,26 @@ hipError_t launch_epi_solve(const EpiArgs& a, uint32_t n_pairs, hipStream_t st);
 hipError_t launch_epi_score(const EpiArgs& a, uint32_t n_pairs, hipStream_t st);
 hipError_t launch_epi_mask(const EpiArgs& a, uint32_t n_pairs, uint32_t max_n, hipStream_t st);
 
+// ---- relative pose of the verified pairs (lcm_pose.hip): src/main.cpp:1405-1409 ------------------------------------------
+// Pair p owns the records pts[offsets[p] .. offsets[p + 1]) as above and the matrix E[p * e_stride ..] (9 doubles, row-major:
+// e_stride = 9 for a packed array, 11 for the EpiResult records k_epi_mask writes).  mask_in (NULL: every record): the
+// records whose byte is non-zero take part.  results: one PoseResult (lcm_pose_device.h) per pair; mask_out: one byte per
+// record.  cand_R / cand_t (NULL: not wanted): the four candidates of every pair, 36 and 12 doubles.
+struct PoseArgs {
+    const uint4*    pts;
+    const uint64_t* offsets;     // n_pairs + 1
+    const double*   E;
+    uint32_t        e_stride;    // doubles between two pairs' matrices
+    const uint8_t*  mask_in;
+    void*           results;
+    uint8_t*        mask_out;
+    double*         cand_R;
+    double*         cand_t;
+    double          fx, fy, cx, cy, max_depth;
+    uint32_t        pair_base;   // set by the launcher: pair of blockIdx.y == 0 (slices of grid_y_limit() pairs)
+};
+hipError_t launch_pose_recover(const PoseArgs& a, uint32_t n_pairs, hipStream_t st);
+
 // ---- bulk / online loop search scored with Lowe's ratio test (lcm_ratio.hip): src/main.cpp:1375-1388 -------------------
 // One workgroup = one WorkItem (or an implicit run of stored slots for ONE query frame, as ScoreArgs' implicit items):
 // per pair, good_count = number of query rows with best < ratio * second (knnMatch(k = 2) order, the second smallest
