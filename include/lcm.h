@@ -504,6 +504,83 @@ LCM_API int  lcm_epi_db_detect_loops(lcm_handle* h, int curr, const uint8_t* que
                                      size_t* n_pairs_out, lcm_epi_result* results, lcm_dmatch* out, lcm_point_pair* pts,
                                      uint8_t* mask, size_t cap, size_t* offsets);
 
+/* ---- loop verification, second step: the RANSAC's best hypotheses refitted on their inliers (local optimisation) --------- */
+/* The eight-point hypothesis of a minimal sample is as noisy as its eight keypoints: with a third of a pixel of noise no
+ * hypothesis of the RANSAC above gathers the inliers the true E has, and the verdict is lost.  lcm_lo_* run that RANSAC
+ * unchanged and then refit its LCM_LO_SEEDS best hypotheses on their own inliers (LO-RANSAC, lcm_lo_device.h).
+ * Per pair, from its records, its `iters` hypotheses E[it] and their inlier counts cnt[it] (the RANSAC's own bytes), with
+ * t = threshold / ((fx + fy) / 2) and "inlier under m" = the inlier rule above with t2 = (t m)^2:
+ *   seeds       the 64 hypotheses with the largest keys (cnt << 16 | 0xFFFF - it), the RANSAC's selection key; seed l has the
+ *               l-th largest.  Integers only
+ *   round r     (r < rounds, multiplier mult[r]) of a seed, from cur = E[seed]:
+ *               S = the records that are inliers of cur under mult[r]; fewer than 8: the seed stops
+ *               per side over S: mean (mx, my), v = mean of (x - mx)^2 + (y - my)^2, s = sqrt(2 / v); v below 1e-20 (the
+ *               rounding of the mean, not a spread), NaN or infinite on either side: the seed stops (LCM_LO_DEGENERATE);
+ *               T = [[s, 0, -s mx], [0, s, -s my], [0, 0, 1]]
+ *               M = the sum over S, in record order, of r r^T for the constraint row r = (c a, c b, c, d a, d b, d, a, b, 1) of
+ *               the normalised x1' = T1 x1 = (a, b, 1), x2' = T2 x2 = (c, d, 1); f = the eigenvector of M's smallest eigenvalue
+ *               (cyclic Jacobi, 8 sweeps); F = T2^T mat(f) T1; E' = F with its singular values forced to (1, 1, 0), as the
+ *               solver's; without a second singular value the seed stops
+ *               cur = E' whether or not it is better; c' = the inliers of E' under the model's own t2 (multiplier 1)
+ *   seed's best the first (c', r) with the strictly largest c'; before round 0 the seed itself with cnt[seed] and round -1
+ *   result      the largest count over the 64 seeds, among equals the lowest l, within a seed the earliest round: n_inliers
+ *               is never below the RANSAC's.  Nothing strictly better: the RANSAC's record byte for byte (E, n_inliers,
+ *               best_iter) and round -1.  The mask is the inlier rule of the winning E under t2
+ * In double, every product and sum rounded on its own.  A pair with fewer than 8 records passes through as LCM_EPI_TOO_FEW
+ * (info.status LCM_LO_TOO_FEW); a pair whose records ALL TOGETHER fail the spread test on a side (identical keypoints) has
+ * no subset that passes it: it passes through with info.status LCM_LO_DEGENERATE. */
+#define LCM_LO_SEEDS 64
+typedef struct lcm_lo_params {
+    int32_t  rounds;            /* 4: in [1, 8] */
+    int32_t  seeds;             /* 64: the only accepted value */
+    double   mult[8];           /* {3, 2, 1.5, 1}: round r's threshold multiplier, finite and >= 1 for r < rounds */
+    uint32_t reserved[6];
+} lcm_lo_params;                /* 96 bytes */
+typedef enum lcm_lo_status { LCM_LO_OK = 0, LCM_LO_TOO_FEW = 1, LCM_LO_DEGENERATE = 2, LCM_LO_NO_MODEL = 3 } lcm_lo_status;
+typedef struct lcm_lo_info {
+    int32_t seed_iter;          /* the hypothesis the winning seed started from (= the result's best_iter) */
+    int32_t round;              /* the winning round, -1 = the RANSAC's record kept */
+    int32_t n_inliers_ransac;   /* what lcm_epi_verify_pairs reports for the pair */
+    int32_t status;             /* lcm_lo_status of the pair: LCM_LO_OK, LCM_LO_TOO_FEW or LCM_LO_DEGENERATE */
+} lcm_lo_info;                  /* 16 bytes */
+LCM_API extern void lcm_lo_params_default(lcm_lo_params* p);
+/* lcm_epi_verify_pairs plus the optimisation: results are lcm_epi_result records (lcm_epi_loop_test, lcm_pose_* and
+ * lcm_pose_best take them unchanged; best_iter = the winning seed's hypothesis), info: n_pairs records, mask as there.
+ * lp == NULL: the defaults (in every call of the family).  Refusals as lcm_epi_verify_pairs's, and a bad lp: nothing is
+ * written.  lcm_last_launch_info: kernel_ms is the five kernels' (the RANSAC's three, k_lo_select, k_lo_refine). */
+LCM_API extern int lcm_lo_verify_pairs(lcm_handle* h, const lcm_point_pair* pts, const size_t* offsets, int n_pairs,
+                                       const lcm_epi_params* ep, const lcm_lo_params* lp, lcm_epi_result* results,
+                                       lcm_lo_info* info, uint8_t* mask);
+/* Test seams.  lcm_lo_select: the selection kernel on caller-supplied counts (iters of them, each in [0, 65535]; iters a
+ * multiple of 64 in [64, 65536]): seeds_out[l] = the hypothesis of the l-th largest key.  lcm_lo_refit_models: ONE round
+ * under the multiplier `mult` for each of n_models (1 .. 64) caller-supplied models E_in = n_models x 9 over n records:
+ * E_out = n_models x 9 (all zero unless status is LCM_LO_OK), n_selected = |S|, status = LCM_LO_OK, LCM_LO_TOO_FEW (|S| < 8),
+ * LCM_LO_DEGENERATE or LCM_LO_NO_MODEL (no second singular value). */
+LCM_API extern int lcm_lo_select(lcm_handle* h, const int32_t* counts, int iters, int32_t* seeds_out);
+LCM_API extern int lcm_lo_refit_models(lcm_handle* h, const lcm_point_pair* pts, int n, const double* E_in, int n_models,
+                                       double mult, const lcm_epi_params* ep, double* E_out, int32_t* n_selected,
+                                       int32_t* status);
+/* lcm_pose_db_verify_pairs (declared below) with the optimisation between the RANSAC and the pose kernel: everything before the
+ * RANSAC (lists, points, offsets) is byte for byte lcm_l2_db_match_points's, results / info / mask are lcm_lo_verify_pairs's on
+ * the returned points, pose_results / pose_mask lcm_pose_recover_pairs's on the optimised E and mask.  `cap` too small: as
+ * there.  lcm_last_launch_info: the two kernels added to launches and to aux_kernel_ms. */
+struct lcm_pose_params;
+struct lcm_pose_result;
+LCM_API extern int lcm_lo_db_verify_pairs(lcm_handle* h, const lcm_pair_ref* slots, int n_pairs, double ratio,
+                                          const lcm_epi_params* ep, const lcm_lo_params* lp, const struct lcm_pose_params* pp,
+                                          lcm_epi_result* results, lcm_lo_info* info, struct lcm_pose_result* pose_results,
+                                          lcm_dmatch* out, lcm_point_pair* pts, uint8_t* mask, uint8_t* pose_mask, size_t cap,
+                                          size_t* offsets);
+/* lcm_pose_db_detect_loops (declared below) likewise: info holds cand_cap records, *best = lcm_pose_best over the optimised
+ * records. */
+LCM_API extern int lcm_lo_db_detect_loops(lcm_handle* h, int curr, const uint8_t* query, const float* query_pts, int nq,
+                                          const uint8_t* skip, int loop_gap, const struct lcm_ratio_loop_params* rp,
+                                          const lcm_epi_params* ep, const lcm_lo_params* lp, const struct lcm_pose_params* pp,
+                                          lcm_loop_candidate* cands, size_t cand_cap, size_t* n_cands, size_t* n_pairs_out,
+                                          lcm_epi_result* results, lcm_lo_info* info, struct lcm_pose_result* pose_results,
+                                          lcm_dmatch* out, lcm_point_pair* pts, uint8_t* mask, uint8_t* pose_mask, size_t cap,
+                                          size_t* offsets, int floor_inliers, int* best);
+
 /* ---- the loop's relative pose on the device, and the best loop ------------------------------------------------------------ */
 /* src/main.cpp:1405-1421: poseInliers = recoverPose(E, ptsCurr, ptsPast, K, R_loop, t_loop, mask), the verdict
  * `poseInliers > 100`, and the globalBest* update.  This is NOT cv::recoverPose bit for bit (OpenCV decomposes by SVD and

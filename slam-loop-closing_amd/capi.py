@@ -91,6 +91,21 @@ class PoseResult(C.Structure):
 POSE_OK, POSE_NO_MODEL = 0, 1            # lcm_pose_status
 
 
+class LoParams(C.Structure):
+    """lcm_lo_params: the rounds of the RANSAC's local optimisation and their threshold multipliers (96 bytes)."""
+    _fields_ = [("rounds", C.c_int32), ("seeds", C.c_int32), ("mult", C.c_double * 8), ("reserved", C.c_uint32 * 6)]
+
+
+class LoInfo(C.Structure):
+    """lcm_lo_info: which seed and round won a pair (round -1: the RANSAC's record kept), the RANSAC's count, the pair's
+    status (16 bytes)."""
+    _fields_ = [("seed_iter", C.c_int32), ("round", C.c_int32), ("n_inliers_ransac", C.c_int32), ("status", C.c_int32)]
+
+
+LO_SEEDS = 64
+LO_OK, LO_TOO_FEW, LO_DEGENERATE, LO_NO_MODEL = 0, 1, 2, 3      # lcm_lo_status
+
+
 class L2DbInfo(C.Structure):
     """lcm_l2_db_info: the SIFT keyframe store's occupancy and the table bytes of its last search."""
     _fields_ = [("frames", C.c_int32), ("reserved_", C.c_int32), ("tiles_used", C.c_uint64), ("tiles_reserved", C.c_uint64),
@@ -131,6 +146,8 @@ assert EPI_RESULT_DTYPE.itemsize == C.sizeof(EpiResult) == 88 and C.sizeof(EpiPa
 POSE_RESULT_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("counts", "<i4", (4,)), ("n_used", "<i4"), ("n_good", "<i4"),
                               ("choice", "<i4"), ("status", "<i4")])          # lcm_pose_result
 assert POSE_RESULT_DTYPE.itemsize == C.sizeof(PoseResult) == 128 and C.sizeof(PoseParams) == 32
+LO_INFO_DTYPE = np.dtype([("seed_iter", "<i4"), ("round", "<i4"), ("n_inliers_ransac", "<i4"), ("status", "<i4")])    # lcm_lo_info
+assert LO_INFO_DTYPE.itemsize == C.sizeof(LoInfo) == 16 and C.sizeof(LoParams) == 96
 assert SCORE_DTYPE.itemsize == C.sizeof(Score) == 8
 assert L2_SCORE_DTYPE.itemsize == 8
 assert C.sizeof(PointPair) == 16          # returned as float32[n, 4]: (qx, qy, tx, ty)
@@ -209,6 +226,16 @@ _SIGNATURES = {
     "lcm_epi_db_detect_loops": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(RatioLoopParams),
                                            C.POINTER(EpiParams), _vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                            _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "lcm_lo_params_default": (None, [C.POINTER(LoParams)]),
+    "lcm_lo_verify_pairs": (C.c_int, [_vp, _vp, _vp, C.c_int, C.POINTER(EpiParams), C.POINTER(LoParams), _vp, _vp, _vp]),
+    "lcm_lo_select": (C.c_int, [_vp, _vp, C.c_int, _vp]),
+    "lcm_lo_refit_models": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_double, C.POINTER(EpiParams), _vp, _vp, _vp]),
+    "lcm_lo_db_verify_pairs": (C.c_int, [_vp, _vp, C.c_int, C.c_double, C.POINTER(EpiParams), C.POINTER(LoParams),
+                                          C.POINTER(PoseParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "lcm_lo_db_detect_loops": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(RatioLoopParams),
+                                          C.POINTER(EpiParams), C.POINTER(LoParams), C.POINTER(PoseParams), _vp, C.c_size_t,
+                                          C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          C.c_size_t, _vp, C.c_int, _i32p]),
     "lcm_pose_params_default": (None, [C.POINTER(PoseParams)]),
     "lcm_pose_loop_test": (C.c_int, [C.POINTER(EpiResult), C.POINTER(PoseResult), C.POINTER(EpiParams), C.POINTER(PoseParams)]),
     "lcm_pose_best": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(EpiParams), C.POINTER(PoseParams), C.c_int, _i32p]),
@@ -344,6 +371,19 @@ def epi_loop_test(result, ep: EpiParams) -> bool:
         r.n_points, r.n_inliers, r.best_iter, r.status = (int(result[k]) for k in ("n_points", "n_inliers", "best_iter", "status"))
         result = r
     return bool(load_library().lcm_epi_loop_test(C.byref(result), C.byref(ep)))
+
+
+def default_lo_params(rounds: Optional[int] = None, mult: Optional[Sequence[float]] = None) -> LoParams:
+    """lcm_lo_params_default (4 rounds, multipliers 3, 2, 1.5, 1; 64 seeds) with the rounds and / or multipliers given."""
+    p = LoParams()
+    load_library().lcm_lo_params_default(C.byref(p))
+    if mult is not None:
+        for r, m in enumerate(mult):
+            p.mult[r] = float(m)
+        p.rounds = len(mult)
+    if rounds is not None:
+        p.rounds = int(rounds)
+    return p
 
 
 def default_pose_params(**over) -> PoseParams:
@@ -1010,6 +1050,116 @@ class Matcher:
                                                  mask.ctypes.data_as(_vp), cap, offs.ctypes.data_as(_vp)))
         total = int(offs[n.value])
         return cands[: n.value], npairs.value, results[: n.value], out[:total], pts[:total], mask[:total], offs[: n.value + 1]
+
+    # -- loop verification, second step: the RANSAC's best hypotheses refitted on their inliers (lcm_lo_*) --
+    def lo_verify_pairs(self, pts, offsets, ep: EpiParams, lp: Optional[LoParams] = None, want_mask: bool = True):
+        """epi_verify_pairs plus the local optimisation: (EPI_RESULT_DTYPE[n_pairs], LO_INFO_DTYPE[n_pairs], uint8[total]
+        inlier mask or None)."""
+        offs = np.ascontiguousarray(offsets, np.uintp)
+        n = len(offs) - 1
+        p = _point_pairs(pts)
+        assert n >= 0 and len(p) >= (int(offs[n]) if n >= 0 else 0)
+        res = np.zeros(max(n, 1), EPI_RESULT_DTYPE)
+        info = np.zeros(max(n, 1), LO_INFO_DTYPE)
+        mask = np.zeros(max(int(offs[n]), 1), np.uint8) if want_mask else None
+        _check(self._lib.lcm_lo_verify_pairs(self._h, _ptr(p), offs.ctypes.data_as(_vp), n, C.byref(ep),
+                                             None if lp is None else C.byref(lp), res.ctypes.data_as(_vp), info.ctypes.data_as(_vp),
+                                             None if mask is None else mask.ctypes.data_as(_vp)))
+        return res[:n], info[:n], (None if mask is None else mask[: int(offs[n])])
+
+    def lo_select(self, counts) -> np.ndarray:
+        """The selection kernel on caller-supplied counts int32[iters]: int32[64], the hypotheses of the 64 largest keys
+        (count << 16 | 0xFFFF - hypothesis), largest first."""
+        c = np.ascontiguousarray(counts, np.int32)
+        seeds = np.zeros(LO_SEEDS, np.int32)
+        _check(self._lib.lcm_lo_select(self._h, _ptr(c), len(c), seeds.ctypes.data_as(_vp)))
+        return seeds
+
+    def lo_refit_models(self, pts, E, mult: float, ep: EpiParams):
+        """ONE refit round under the multiplier `mult` for each of the models E float64[n_models <= 64, 9] over the point
+        pairs: (float64[n_models, 9] refits, int32[n_models] records selected, int32[n_models] lcm_lo_status)."""
+        p = _point_pairs(pts)
+        e = np.ascontiguousarray(E, np.float64).reshape(-1, 9)
+        n = len(e)
+        out, n_sel, status = np.zeros((max(n, 1), 9)), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        _check(self._lib.lcm_lo_refit_models(self._h, _ptr(p), len(p), _ptr(e), n, float(mult), C.byref(ep), out.ctypes.data_as(_vp),
+                                             n_sel.ctypes.data_as(_vp), status.ctypes.data_as(_vp)))
+        return out[:n], n_sel[:n], status[:n]
+
+    def lo_db_verify_pairs(self, pairs: Sequence[Tuple[int, int]], ratio: float, ep: EpiParams, lp: Optional[LoParams] = None,
+                           pp: Optional[PoseParams] = None, cap: Optional[int] = None, out: Optional[np.ndarray] = None,
+                           pts: Optional[np.ndarray] = None, results: Optional[np.ndarray] = None, info: Optional[np.ndarray] = None,
+                           mask: Optional[np.ndarray] = None, pose_results: Optional[np.ndarray] = None,
+                           pose_mask: Optional[np.ndarray] = None):
+        """pose_db_verify_pairs with the local optimisation between the RANSAC and the pose recovery: (EPI_RESULT_DTYPE[n],
+        LO_INFO_DTYPE[n], POSE_RESULT_DTYPE[n], DMATCH_DTYPE[total], float32[total, 4], uint8[total] inlier mask, uint8[total]
+        pose mask, offsets[n + 1]).  out / pts / results / info / mask / pose_results / pose_mask: the caller's buffers."""
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n = pr.shape[0]
+        if cap is None:
+            if out is not None:
+                cap = len(out)
+            else:
+                size = self.l2_db_size()
+                cap = sum(self.l2_db_rows(int(q)) for q in pr[:, 0] if 0 <= q < size)
+        out = np.zeros(max(cap, 1), DMATCH_DTYPE) if out is None else out
+        pts = np.zeros((max(cap, 1), 4), np.float32) if pts is None else pts
+        results = np.zeros(max(n, 1), EPI_RESULT_DTYPE) if results is None else results
+        info = np.zeros(max(n, 1), LO_INFO_DTYPE) if info is None else info
+        mask = np.zeros(max(cap, 1), np.uint8) if mask is None else mask
+        pose_results = np.zeros(max(n, 1), POSE_RESULT_DTYPE) if pose_results is None else pose_results
+        pose_mask = np.zeros(max(cap, 1), np.uint8) if pose_mask is None else pose_mask
+        assert out.dtype == DMATCH_DTYPE and out.flags["C_CONTIGUOUS"] and len(out) >= cap
+        assert pts.dtype == np.float32 and pts.flags["C_CONTIGUOUS"] and pts.shape[1:] == (4,) and len(pts) >= cap
+        assert results.dtype == EPI_RESULT_DTYPE and len(results) >= n and mask.dtype == np.uint8 and len(mask) >= cap
+        assert info.dtype == LO_INFO_DTYPE and len(info) >= n
+        assert pose_results.dtype == POSE_RESULT_DTYPE and len(pose_results) >= n and pose_mask.dtype == np.uint8 and len(pose_mask) >= cap
+        offs = np.zeros(n + 1, np.uintp)
+        self.last_offsets = offs
+        _check(self._lib.lcm_lo_db_verify_pairs(self._h, _ptr(pr), n, ratio, C.byref(ep), None if lp is None else C.byref(lp),
+                                                None if pp is None else C.byref(pp), results.ctypes.data_as(_vp),
+                                                info.ctypes.data_as(_vp), pose_results.ctypes.data_as(_vp), out.ctypes.data_as(_vp),
+                                                pts.ctypes.data_as(_vp), mask.ctypes.data_as(_vp), pose_mask.ctypes.data_as(_vp), cap,
+                                                offs.ctypes.data_as(_vp)))
+        total = int(offs[n])
+        return results[:n], info[:n], pose_results[:n], out[:total], pts[:total], mask[:total], pose_mask[:total], offs
+
+    def lo_db_detect_loops(self, curr: int, loop_gap: int, ep: EpiParams, lp: Optional[LoParams] = None,
+                           pp: Optional[PoseParams] = None, floor_inliers: int = -1, query=None, query_pts=None, skip=None,
+                           ratio: Optional[float] = None, min_rows: Optional[int] = None, min_matches: Optional[int] = None,
+                           cand_cap: Optional[int] = None, cap: Optional[int] = None):
+        """pose_db_detect_loops with the local optimisation between the RANSAC and the pose recovery: (candidates, pairs scored,
+        EPI_RESULT_DTYPE[n_candidates], LO_INFO_DTYPE[n_candidates], POSE_RESULT_DTYPE[n_candidates], DMATCH_DTYPE[total],
+        float32[total, 4], uint8[total] inlier mask, uint8[total] pose mask, offsets[n_candidates + 1], best)."""
+        rpp, _rp, sk, cand_cap, cands = self._l2_db_search_args(skip, ratio, min_rows, min_matches, cand_cap, None)
+        q = None if query is None else _sift_rows(query)
+        nq = 0 if q is None else q.shape[0]
+        qp = None if q is None else (q if q.size else np.zeros((1, SIFT_BYTES), np.uint8)).ctypes.data_as(_vp)
+        kp = None if (q is None or query_pts is None) else self._kp(query_pts, nq)
+        kpp = None if kp is None else (kp if kp.size else np.zeros((1, 2), np.float32)).ctypes.data_as(_vp)
+        if cap is None:
+            rows_q = nq if q is not None else (self.l2_db_rows(curr) if 0 <= curr < self.l2_db_size() else 0)
+            cap = rows_q * max(min(cand_cap, self.l2_db_size()), 1)
+        out = np.zeros(max(cap, 1), DMATCH_DTYPE)
+        pts = np.zeros((max(cap, 1), 4), np.float32)
+        mask = np.zeros(max(cap, 1), np.uint8)
+        pose_mask = np.zeros(max(cap, 1), np.uint8)
+        results = np.zeros(max(cand_cap, 1), EPI_RESULT_DTYPE)
+        info = np.zeros(max(cand_cap, 1), LO_INFO_DTYPE)
+        pose_results = np.zeros(max(cand_cap, 1), POSE_RESULT_DTYPE)
+        offs = np.zeros(cand_cap + 1, np.uintp)
+        n, npairs, best = C.c_size_t(0), C.c_size_t(0), C.c_int32(-1)
+        self.last_offsets, self.last_n_cands = offs, n
+        _check(self._lib.lcm_lo_db_detect_loops(self._h, curr, qp, kpp, nq, _ptr(sk), loop_gap, rpp, C.byref(ep),
+                                                None if lp is None else C.byref(lp), None if pp is None else C.byref(pp),
+                                                cands.ctypes.data_as(_vp), cand_cap, C.byref(n), C.byref(npairs),
+                                                results.ctypes.data_as(_vp), info.ctypes.data_as(_vp),
+                                                pose_results.ctypes.data_as(_vp), out.ctypes.data_as(_vp), pts.ctypes.data_as(_vp),
+                                                mask.ctypes.data_as(_vp), pose_mask.ctypes.data_as(_vp), cap,
+                                                offs.ctypes.data_as(_vp), floor_inliers, C.byref(best)))
+        total = int(offs[n.value])
+        return (cands[: n.value], npairs.value, results[: n.value], info[: n.value], pose_results[: n.value], out[:total],
+                pts[:total], mask[:total], pose_mask[:total], offs[: n.value + 1], best.value)
 
     # -- the loop's relative pose on the device and the best loop (lcm_pose_*) --
     def pose_recover_pairs(self, pts, offsets, E, ep: EpiParams, pp: Optional[PoseParams] = None, mask_in=None,

@@ -37,12 +37,16 @@ static int epi_reserve(lcm_handle* h, size_t n_pairs, size_t iters, size_t total
 }
 
 int epi_enqueue(lcm_handle* h, const uint4* d_pts, const uint64_t* d_off, size_t n_pairs, uint32_t max_n, size_t total,
-                const lcm_epi_params& ep, uint32_t* launches) {
+                const lcm_epi_params& ep, uint32_t* launches, bool want_counts) {
     *launches = 0;
     if (n_pairs == 0) return LCM_OK;
     if (n_pairs > 0x7FFFFFFFull) return fail(LCM_ERR_CAPACITY, "too many pairs for one call");
     int rc = epi_reserve(h, n_pairs, (size_t)ep.iters, total); if (rc) return rc;
-    const EpiArgs a = epi_args(h, d_pts, d_off, ep, (uint32_t)ep.iters);
+    EpiArgs a = epi_args(h, d_pts, d_off, ep, (uint32_t)ep.iters);
+    if (want_counts) {
+        rc = ensure_dev(h->epi.d_counts, h->epi.d_counts_n, n_pairs * (size_t)ep.iters); if (rc) return rc;
+        a.counts = h->epi.d_counts;
+    }
     HIP_TRY(hipMemsetAsync(a.best, 0, n_pairs * sizeof(uint32_t), h->stream));
     hipError_t e = launch_epi_solve(a, (uint32_t)n_pairs, h->stream);
     if (e == hipSuccess) e = launch_epi_score(a, (uint32_t)n_pairs, h->stream);

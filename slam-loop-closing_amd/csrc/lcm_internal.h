@@ -9,6 +9,7 @@
 //                      the SIFT keyframe store (lcm_l2_db_*)
 //   lcm_epi.cpp        essential-matrix RANSAC over the loop candidates' correspondences (lcm_epi_*)
 //   lcm_pose.cpp       relative pose of the verified candidates and the best loop (lcm_pose_*)
+//   lcm_lo.cpp         local optimisation of the RANSAC's best hypotheses (lcm_lo_*)
 // Not installed; the public surface is include/lcm.h.
 #pragma once
 #include "../../include/lcm.h"
@@ -286,6 +287,13 @@ struct lcm_handle {
         lcm_pose_result* d_res = nullptr; size_t d_res_n = 0;
         uint8_t* d_mask = nullptr;    size_t d_mask_n = 0;
     } pose;
+    // local optimisation (lcm_lo.cpp): the seeds (64 per pair), the info records, and the seams' models and outputs
+    struct LoScratch {
+        int32_t* d_seeds = nullptr;   size_t d_seeds_n = 0;
+        lcm_lo_info* d_info = nullptr; size_t d_info_n = 0;
+        double* d_models = nullptr;   size_t d_models_n = 0;     // the refit seam: 64 x 9 in, 64 x 9 out
+        int32_t* d_seam = nullptr;    size_t d_seam_n = 0;       // ... and 64 counts + 64 statuses
+    } lo;
     lcm_launch_info info{};
     bool info_pending = false;
 };
@@ -414,13 +422,23 @@ int batch_jobs(lcm_handle* h, const uint8_t* q_host, int nq_host, const lcm_pair
 int epi_params_checked(const lcm_epi_params* ep);
 // Enqueues k_epi_solve, k_epi_score and k_epi_mask on h's stream over n_pairs pairs whose records d_pts[d_off[p] .. d_off[p + 1])
 // are on the device (max_n = the longest pair, total = d_off[n_pairs]); results -> h->epi.d_res, mask -> h->epi.d_mask.
-// *launches = kernel launches made.  No host wait.
+// *launches = kernel launches made.  No host wait.  want_counts: every hypothesis's inlier count -> h->epi.d_counts as well
+// (what lo_enqueue reads).
 int epi_enqueue(lcm_handle* h, const uint4* d_pts, const uint64_t* d_off, size_t n_pairs, uint32_t max_n, size_t total,
-                const lcm_epi_params& ep, uint32_t* launches);
+                const lcm_epi_params& ep, uint32_t* launches, bool want_counts = false);
 // Copies of the last epi_enqueue's records to the host, enqueued (the caller waits); mask may be NULL
 int epi_download(lcm_handle* h, size_t n_pairs, size_t total, lcm_epi_result* results, uint8_t* mask);
 // A host call's records and offsets -> h->epi.d_pts / d_off, enqueued (the sources are pageable: the caller waits)
 int epi_upload_points(lcm_handle* h, const lcm_point_pair* pts, const size_t* offsets, size_t n_pairs, size_t total);
+// ---- lcm_lo.cpp: the local optimisation behind lcm_lo_*; lcm_l2.cpp runs it between the RANSAC and the pose recovery
+// NULL or checked parameters -> *out (the defaults for NULL)
+int lo_params_checked(const lcm_lo_params* lp, lcm_lo_params* out);
+// Enqueues k_lo_select and k_lo_refine on h's stream behind an epi_enqueue(..., want_counts = true) over the same pairs: they
+// read h->epi.d_E / d_counts and rewrite h->epi.d_res / d_mask where a refit is better; info -> h->lo.d_info.  No host wait.
+int lo_enqueue(lcm_handle* h, const uint4* d_pts, const uint64_t* d_off, size_t n_pairs, const lcm_epi_params& ep,
+               const lcm_lo_params& lp, uint32_t* launches);
+// Copy of the last lo_enqueue's info records to the host, enqueued (the caller waits)
+int lo_download(lcm_handle* h, size_t n_pairs, lcm_lo_info* info);
 // ---- lcm_pose.cpp: the pose recovery behind lcm_pose_*; lcm_l2.cpp runs it on the RANSAC's records
 // pp checked (LCM_ERR_INVALID_ARG and the message otherwise); *out = pp's values, or the defaults for NULL
 int pose_params_checked(const lcm_pose_params* pp, lcm_pose_params* out);

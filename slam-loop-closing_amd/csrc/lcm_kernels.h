@@ -316,6 +316,34 @@ struct PoseArgs {
 };
 hipError_t launch_pose_recover(const PoseArgs& a, uint32_t n_pairs, hipStream_t st);
 
+// ---- local optimisation of the RANSAC's best hypotheses (lcm_lo.hip): refits on the inliers, between the two above ---------
+// Pair p owns its records as above, the RANSAC's hypotheses E[(p * iters + it) * 9 ..] and their counts[p * iters + it].
+// k_lo_select writes seeds[p * 64 + lane] = the hypothesis of the lane-th largest key; k_lo_refine reads them and overwrites
+// results[p] and the pair's mask bytes (k_epi_mask's) only where a refit holds strictly more inliers, and writes info[p].
+// The refit seam (refit_E != NULL, one pair): E holds n_models <= 64 models instead, model m = lane m runs ONE round under
+// mult[0] and writes refit_E[9 m ..], refit_n[m] (records selected) and refit_status[m]; nothing else is written.
+struct LoArgs {
+    const uint4*    pts;
+    const uint64_t* offsets;     // n_pairs + 1
+    const double*   E;
+    const uint32_t* counts;
+    int32_t*        seeds;
+    void*           results;     // EpiResult (lcm_epi_device.h) per pair
+    uint8_t*        mask;
+    void*           info;        // LoInfo (lcm_lo_device.h) per pair
+    double*         refit_E;
+    int32_t*        refit_n;
+    int32_t*        refit_status;
+    double          fx, fy, cx, cy, t;       // t = threshold / ((fx + fy) / 2)
+    double          mult[8];
+    uint32_t        iters;       // multiple of 64
+    uint32_t        rounds;      // 1 .. 8
+    uint32_t        n_models;    // the seam's
+    uint32_t        pair_base;   // set by the launchers: pair of blockIdx.y == 0 (slices of grid_y_limit() pairs)
+};
+hipError_t launch_lo_select(const LoArgs& a, uint32_t n_pairs, hipStream_t st);
+hipError_t launch_lo_refine(const LoArgs& a, uint32_t n_pairs, hipStream_t st);
+
 // ---- bulk / online loop search scored with Lowe's ratio test (lcm_ratio.hip): src/main.cpp:1375-1388 -------------------
 // One workgroup = one WorkItem (or an implicit run of stored slots for ONE query frame, as ScoreArgs' implicit items):
 // per pair, good_count = number of query rows with best < ratio * second (knnMatch(k = 2) order, the second smallest

@@ -12,6 +12,7 @@
 #include "lcm_internal.h"
 
 #include "lcm_epi_host.h"
+#include "lcm_lo_host.h"
 #include "lcm_pose_host.h"
 
 #include <cmath>
@@ -784,9 +785,12 @@ static_assert(sizeof(size_t) == sizeof(uint64_t) && sizeof(lcm_dmatch) == sizeof
 // them, pair p of the call seeded with p; its kernels count into `launches` and into the aux events' span.
 // pp != NULL (checked): the pose recovery (lcm_pose.hip) follows k_epi_mask on the same records, the device's results[].E and
 // the device's mask; one more launch per slice, inside the same span.
+// lp != NULL (checked, with info): the local optimisation (lcm_lo.hip) runs between the two, on the RANSAC's hypotheses and
+// counts; it rewrites results[] and the mask where a refit is better, so the pose recovery reads the optimised ones.
 struct EpiWanted {
     const lcm_epi_params* ep; lcm_epi_result* results; uint8_t* mask;
     const lcm_pose_params* pp = nullptr; lcm_pose_result* pose_results = nullptr; uint8_t* pose_mask = nullptr;
+    const lcm_lo_params* lp = nullptr; lcm_lo_info* info = nullptr;
 };
 
 int store_lists(lcm_handle* h, const int* rows, int n_frames, const std::vector<L2Pair>& live, const std::vector<int>& job_of,
@@ -796,6 +800,7 @@ int store_lists(lcm_handle* h, const int* rows, int n_frames, const std::vector<
         std::fill(offsets, offsets + n_pairs + 1, (size_t)0);
         if (epi) lcm::epi_empty_results(epi->results, n_pairs);
         if (epi && epi->pp) lcm::pose_empty_results(epi->pose_results, n_pairs);
+        if (epi && epi->lp) lcm::lo_empty_info(epi->info, n_pairs);
         return LCM_OK;
     }
     L2Store& d = h->l2db;
@@ -852,8 +857,12 @@ int store_lists(lcm_handle* h, const int* rows, int n_frames, const std::vector<
     if (epi) {                                      // a pair's records are at most its query rows: they fit the packed key
         uint32_t max_n = 0, launches = 0;
         for (size_t p = 0; p < n_pairs; ++p) max_n = std::max(max_n, (uint32_t)(offsets[p + 1] - offsets[p]));
-        rc = lcm::epi_enqueue(h, s.d_rec_pts, s.d_offsets, n_pairs, max_n, total, *epi->ep, &launches); if (rc) return rc;
+        rc = lcm::epi_enqueue(h, s.d_rec_pts, s.d_offsets, n_pairs, max_n, total, *epi->ep, &launches, epi->lp != nullptr); if (rc) return rc;
         h->info.launches += launches;
+        if (epi->lp) {
+            rc = lcm::lo_enqueue(h, s.d_rec_pts, s.d_offsets, n_pairs, *epi->ep, *epi->lp, &launches); if (rc) return rc;
+            h->info.launches += launches;
+        }
         if (epi->pp) {
             static_assert(sizeof(lcm_epi_result) == 11 * sizeof(double) && offsetof(lcm_epi_result, E) == 0, "results[].E as a matrix array");
             rc = lcm::pose_enqueue(h, s.d_rec_pts, s.d_offsets, n_pairs, total, reinterpret_cast<const double*>(h->epi.d_res), 11,
@@ -868,6 +877,7 @@ int store_lists(lcm_handle* h, const int* rows, int n_frames, const std::vector<
         if (pts) HIP_TRY(hipMemcpyAsync(pts, s.d_rec_pts, total * sizeof(uint4), hipMemcpyDeviceToHost, h->stream));
     }
     if (epi) { rc = lcm::epi_download(h, n_pairs, total, epi->results, epi->mask); if (rc) return rc; }
+    if (epi && epi->lp) { rc = lcm::lo_download(h, n_pairs, epi->info); if (rc) return rc; }
     if (epi && epi->pp) { rc = lcm::pose_download(h, n_pairs, total, epi->pose_results, epi->pose_mask); if (rc) return rc; }
     if (total || epi) HIP_TRY(hipStreamSynchronize(h->stream));
     return LCM_OK;
@@ -886,6 +896,7 @@ int l2_db_match_points_impl(lcm_handle* h, const lcm_pair_ref* slots, int n_pair
         const int rc = lcm::epi_params_checked(epi->ep); if (rc) return rc;
         if (!pts || (n_pairs > 0 && !epi->results)) return fail(LCM_ERR_INVALID_ARG, "the verification needs pts and results");
         if (epi->pp && n_pairs > 0 && !epi->pose_results) return fail(LCM_ERR_INVALID_ARG, "the pose recovery needs pose_results");
+        if (epi->lp && n_pairs > 0 && !epi->info) return fail(LCM_ERR_INVALID_ARG, "the optimisation needs info");
     }
     offsets[0] = 0;
     int rc = check_knn(h, ratio); if (rc) return rc;
@@ -917,6 +928,7 @@ int l2_db_detect_loops_points_impl(lcm_handle* h, int curr, const uint8_t* query
         const int r = lcm::epi_params_checked(epi->ep); if (r) return r;
         if (!pts || (cand_cap > 0 && !epi->results)) return fail(LCM_ERR_INVALID_ARG, "the verification needs pts and results");
         if (epi->pp && cand_cap > 0 && !epi->pose_results) return fail(LCM_ERR_INVALID_ARG, "the pose recovery needs pose_results");
+        if (epi->lp && cand_cap > 0 && !epi->info) return fail(LCM_ERR_INVALID_ARG, "the optimisation needs info");
     }
     lcm_ratio_loop_params rp;
     int rc = store_search_args(h, loop_gap, rp_in, n_cands, n_pairs_out, &rp); if (rc) return rc;
@@ -1124,6 +1136,39 @@ int lcm_pose_db_detect_loops(lcm_handle* h, int curr, const uint8_t* query, cons
                                             pts, cap, offsets, &w);
         if (rc) return rc;
         *best = lcm::pose_best(results, pose_results, *n_cands, ep, &ppv, floor_inliers);      // src/main.cpp:1403-1418, host only
+        return LCM_OK;
+    });
+}
+int lcm_lo_db_verify_pairs(lcm_handle* h, const lcm_pair_ref* slots, int n_pairs, double ratio, const lcm_epi_params* ep,
+                           const lcm_lo_params* lp, const lcm_pose_params* pp, lcm_epi_result* results, lcm_lo_info* info,
+                           lcm_pose_result* pose_results, lcm_dmatch* out, lcm_point_pair* pts, uint8_t* mask, uint8_t* pose_mask,
+                           size_t cap, size_t* offsets) {
+    return guarded([&] {
+        lcm_pose_params ppv;
+        lcm_lo_params lpv;
+        int rc = lcm::pose_params_checked(pp, &ppv); if (rc) return rc;
+        rc = lcm::lo_params_checked(lp, &lpv); if (rc) return rc;
+        const EpiWanted w{ep, results, mask, &ppv, pose_results, pose_mask, &lpv, info};
+        return l2_db_match_points_impl(h, slots, n_pairs, ratio, out, pts, cap, offsets, &w);
+    });
+}
+int lcm_lo_db_detect_loops(lcm_handle* h, int curr, const uint8_t* query, const float* query_pts, int nq, const uint8_t* skip,
+                           int loop_gap, const lcm_ratio_loop_params* rp, const lcm_epi_params* ep, const lcm_lo_params* lp,
+                           const lcm_pose_params* pp, lcm_loop_candidate* cands, size_t cand_cap, size_t* n_cands, size_t* n_pairs_out,
+                           lcm_epi_result* results, lcm_lo_info* info, lcm_pose_result* pose_results, lcm_dmatch* out,
+                           lcm_point_pair* pts, uint8_t* mask, uint8_t* pose_mask, size_t cap, size_t* offsets, int floor_inliers,
+                           int* best) {
+    return guarded([&]() -> int {
+        lcm_pose_params ppv;
+        lcm_lo_params lpv;
+        int rc = lcm::pose_params_checked(pp, &ppv); if (rc) return rc;
+        rc = lcm::lo_params_checked(lp, &lpv); if (rc) return rc;
+        if (!best) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+        const EpiWanted w{ep, results, mask, &ppv, pose_results, pose_mask, &lpv, info};
+        rc = l2_db_detect_loops_points_impl(h, curr, query, query_pts, nq, skip, loop_gap, rp, cands, cand_cap, n_cands, n_pairs_out, out,
+                                            pts, cap, offsets, &w);
+        if (rc) return rc;
+        *best = lcm::pose_best(results, pose_results, *n_cands, ep, &ppv, floor_inliers);
         return LCM_OK;
     });
 }
