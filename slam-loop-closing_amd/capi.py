@@ -472,6 +472,19 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None or a.size == 0 else a.ctypes.data_as(_vp)
 
 
+def _ref(p: Optional[C.Structure]):
+    return None if p is None else C.byref(p)
+
+
+def _buffer(a: Optional[np.ndarray], dtype, rows: int, *tail, contiguous: bool = False) -> np.ndarray:
+    """The caller's buffer a, checked (dtype, room for `rows` rows; row shape and layout where the call depends on them), or a
+    new one of at least one row."""
+    if a is None:
+        return np.zeros((max(rows, 1), *tail), dtype)
+    assert a.dtype == dtype and len(a) >= rows and (not contiguous or a.flags["C_CONTIGUOUS"]) and (not tail or a.shape[1:] == tail)
+    return a
+
+
 def _sift_rows(a) -> np.ndarray:
     a = np.asarray(a)
     if a.dtype != np.uint8:
@@ -900,31 +913,81 @@ class Matcher:
         _check(self._lib.lcm_l2_db_read_kp(self._h, slot, out.ctypes.data_as(_vp), out.shape[0]))
         return out
 
+    # -- what the store's list calls share.  Their C signatures are regular: [the stages' parameters], then (the candidate
+    # search's arguments,) the per-pair records of the stages, out, pts, the stages' masks, cap, offsets (, floor_inliers, best) --
+    @staticmethod
+    def _list_buffers(cap: int, n: int, points: bool = True, epi: bool = False, lo: bool = False, pose: bool = False, out=None,
+                      pts=None, results=None, info=None, mask=None, pose_results=None, pose_mask=None):
+        """The buffers of a list call with room for cap records of n pairs (or candidates), the caller's (checked) or new ones,
+        in the order of the C signatures and of the returned tuples: ([per-pair records of the stages epi / lo / pose that the
+        call runs], [out, pts (None without points), the stages' masks])."""
+        if points or pts is not None:
+            pts = _buffer(pts, np.float32, cap, 4, contiguous=True)
+        per_pair, per_record = [], [_buffer(out, DMATCH_DTYPE, cap, contiguous=True), pts if points else None]
+        if epi:
+            per_pair.append(_buffer(results, EPI_RESULT_DTYPE, n))
+            per_record.append(_buffer(mask, np.uint8, cap))
+        if lo:
+            per_pair.append(_buffer(info, LO_INFO_DTYPE, n))
+        if pose:
+            per_pair.append(_buffer(pose_results, POSE_RESULT_DTYPE, n))
+            per_record.append(_buffer(pose_mask, np.uint8, cap))
+        return per_pair, per_record
+
+    @staticmethod
+    def _list_slices(per_pair, per_record, n: int, total: int) -> list:
+        return [a[:n] for a in per_pair] + [None if a is None else a[:total] for a in per_record]
+
+    def _db_pairs_call(self, fn, params: tuple, pairs, ratio: float, cap: Optional[int], out=None, **bufs):
+        """fn over stored pairs: (the stages' per-pair records, out, pts, the stages' masks, offsets[n + 1]).  cap: given,
+        else the caller's out, else the query sides' rows."""
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n = pr.shape[0]
+        if cap is None and out is not None:
+            cap = len(out)
+        elif cap is None:
+            size = self.l2_db_size()
+            cap = sum(self.l2_db_rows(int(q)) for q in pr[:, 0] if 0 <= q < size)
+        per_pair, per_record = self._list_buffers(cap, n, out=out, **bufs)
+        ptrs = [None if a is None else a.ctypes.data_as(_vp) for a in per_pair + per_record]
+        offs = np.zeros(n + 1, np.uintp)
+        self.last_offsets = offs
+        _check(fn(self._h, _ptr(pr), n, ratio, *params, *ptrs, cap, offs.ctypes.data_as(_vp)))
+        return (*self._list_slices(per_pair, per_record, n, int(offs[n])), offs)
+
+    def _db_detect_call(self, fn, params: tuple, curr: int, loop_gap: int, query, query_pts, skip, ratio, min_rows, min_matches,
+                        cand_cap: Optional[int], cap: Optional[int], cands=None, floor_inliers: Optional[int] = None, out=None, **bufs):
+        """fn for one keyframe: (candidates, pairs scored, then as _db_pairs_call with offsets[n_candidates + 1], then best when
+        floor_inliers is given).  cap: given, else the caller's out, else the keyframe's rows x the candidates there is room for."""
+        rpp, _rp, sk, cand_cap, cands = self._l2_db_search_args(skip, ratio, min_rows, min_matches, cand_cap, cands)
+        q = None if query is None else _sift_rows(query)
+        nq = 0 if q is None else q.shape[0]
+        # an empty host matrix is still the host form: the library tells the two apart by the pointer
+        qp = None if q is None else (q if q.size else np.zeros((1, SIFT_BYTES), np.uint8)).ctypes.data_as(_vp)
+        kp = None if (q is None or query_pts is None) else self._kp(query_pts, nq)
+        kpp = None if kp is None else (kp if kp.size else np.zeros((1, 2), np.float32)).ctypes.data_as(_vp)
+        if cap is None and out is not None:
+            cap = len(out)
+        elif cap is None:
+            rows_q = nq if q is not None else (self.l2_db_rows(curr) if 0 <= curr < self.l2_db_size() else 0)
+            cap = rows_q * max(min(cand_cap, self.l2_db_size()), 1)
+        per_pair, per_record = self._list_buffers(cap, cand_cap, out=out, **bufs)
+        ptrs = [None if a is None else a.ctypes.data_as(_vp) for a in per_pair + per_record]
+        offs = np.zeros(cand_cap + 1, np.uintp)
+        n, npairs, best = C.c_size_t(0), C.c_size_t(0), C.c_int32(-1)
+        self.last_offsets, self.last_n_cands = offs, n
+        tail = () if floor_inliers is None else (floor_inliers, C.byref(best))
+        _check(fn(self._h, curr, qp, kpp, nq, _ptr(sk), loop_gap, rpp, *params, cands.ctypes.data_as(_vp), cand_cap, C.byref(n), C.byref(npairs),
+                  *ptrs, cap, offs.ctypes.data_as(_vp), *tail))
+        lists = self._list_slices(per_pair, per_record, n.value, int(offs[n.value]))
+        return (cands[: n.value], npairs.value, *lists, offs[: n.value + 1], *(() if floor_inliers is None else (best.value,)))
+
     def l2_db_match_points(self, pairs: Sequence[Tuple[int, int]], ratio: float, cap: Optional[int] = None, points: bool = True,
                            out: Optional[np.ndarray] = None, pts: Optional[np.ndarray] = None):
         """l2_db_match_pairs_ratio with the lists made on the device: (DMATCH_DTYPE[total], float32[total, 4] of (qx, qy, tx, ty)
         or None when points is False, offsets[n + 1]).  out / pts: the caller's buffers (cap = their length unless given).
         After LcmError(ERR_CAPACITY), `self.last_offsets[n]` holds the needed record count."""
-        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-        n = pr.shape[0]
-        if cap is None:
-            if out is not None:
-                cap = len(out)
-            else:
-                size = self.l2_db_size()
-                cap = sum(self.l2_db_rows(int(q)) for q in pr[:, 0] if 0 <= q < size)
-        if out is None:
-            out = np.zeros(max(cap, 1), DMATCH_DTYPE)
-        if points and pts is None:
-            pts = np.zeros((max(cap, 1), 4), np.float32)
-        assert out.dtype == DMATCH_DTYPE and out.flags["C_CONTIGUOUS"] and len(out) >= cap
-        assert pts is None or (pts.dtype == np.float32 and pts.flags["C_CONTIGUOUS"] and pts.shape[1:] == (4,) and len(pts) >= cap)
-        offs = np.zeros(n + 1, np.uintp)
-        self.last_offsets = offs
-        _check(self._lib.lcm_l2_db_match_points(self._h, _ptr(pr), n, ratio, out.ctypes.data_as(_vp),
-                                                None if not points else pts.ctypes.data_as(_vp), cap, offs.ctypes.data_as(_vp)))
-        total = int(offs[n])
-        return out[:total], (pts[:total] if points else None), offs
+        return self._db_pairs_call(self._lib.lcm_l2_db_match_points, (), pairs, ratio, cap, points=points, out=out, pts=pts)
 
     def l2_db_detect_loops_points(self, curr: int, loop_gap: int, query=None, query_pts=None, skip=None,
                                   ratio: Optional[float] = None, min_rows: Optional[int] = None, min_matches: Optional[int] = None,
@@ -935,33 +998,8 @@ class Matcher:
         (candidates, pairs scored, DMATCH_DTYPE[total], float32[total, 4] or None, offsets[n_candidates + 1]).  query /
         query_pts: host SIFT rows and their keypoints standing for position `curr` (not stored), or None for the stored
         slot `curr`.  After LcmError(ERR_CAPACITY), `self.last_offsets` / `self.last_n_cands` hold what the call reported."""
-        rpp, _rp, sk, cand_cap, cands = self._l2_db_search_args(skip, ratio, min_rows, min_matches, cand_cap, cands)
-        q = None if query is None else _sift_rows(query)
-        nq = 0 if q is None else q.shape[0]
-        qp = None if q is None else (q if q.size else np.zeros((1, SIFT_BYTES), np.uint8)).ctypes.data_as(_vp)
-        kp = None if (q is None or query_pts is None) else self._kp(query_pts, nq)
-        kpp = None if kp is None else (kp if kp.size else np.zeros((1, 2), np.float32)).ctypes.data_as(_vp)
-        if cap is None:
-            if out is not None:
-                cap = len(out)
-            else:
-                rows_q = nq if q is not None else (self.l2_db_rows(curr) if 0 <= curr < self.l2_db_size() else 0)
-                cap = rows_q * max(min(cand_cap, self.l2_db_size()), 1)
-        if out is None:
-            out = np.zeros(max(cap, 1), DMATCH_DTYPE)
-        if points and pts is None:
-            pts = np.zeros((max(cap, 1), 4), np.float32)
-        assert out.dtype == DMATCH_DTYPE and out.flags["C_CONTIGUOUS"] and len(out) >= cap
-        assert pts is None or (pts.dtype == np.float32 and pts.flags["C_CONTIGUOUS"] and pts.shape[1:] == (4,) and len(pts) >= cap)
-        offs = np.zeros(cand_cap + 1, np.uintp)
-        n, npairs = C.c_size_t(0), C.c_size_t(0)
-        self.last_offsets, self.last_n_cands = offs, n
-        _check(self._lib.lcm_l2_db_detect_loops_points(self._h, curr, qp, kpp, nq, _ptr(sk), loop_gap, rpp, cands.ctypes.data_as(_vp),
-                                                       cand_cap, C.byref(n), C.byref(npairs), out.ctypes.data_as(_vp),
-                                                       None if not points else pts.ctypes.data_as(_vp), cap,
-                                                       offs.ctypes.data_as(_vp)))
-        total = int(offs[n.value])
-        return cands[: n.value], npairs.value, out[:total], (pts[:total] if points else None), offs[: n.value + 1]
+        return self._db_detect_call(self._lib.lcm_l2_db_detect_loops_points, (), curr, loop_gap, query, query_pts, skip, ratio, min_rows,
+                                    min_matches, cand_cap, cap, cands=cands, points=points, out=out, pts=pts)
 
     # -- loop verification: essential-matrix RANSAC on the device (lcm_epi_*) --
     def epi_verify_pairs(self, pts, offsets, ep: EpiParams, want_mask: bool = True):
@@ -1000,56 +1038,16 @@ class Matcher:
                             results: Optional[np.ndarray] = None, mask: Optional[np.ndarray] = None):
         """l2_db_match_points followed by the RANSAC on the device's own point records: (EPI_RESULT_DTYPE[n], DMATCH_DTYPE[total],
         float32[total, 4], uint8[total] mask, offsets[n + 1]).  out / pts / results / mask: the caller's buffers."""
-        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-        n = pr.shape[0]
-        if cap is None:
-            if out is not None:
-                cap = len(out)
-            else:
-                size = self.l2_db_size()
-                cap = sum(self.l2_db_rows(int(q)) for q in pr[:, 0] if 0 <= q < size)
-        out = np.zeros(max(cap, 1), DMATCH_DTYPE) if out is None else out
-        pts = np.zeros((max(cap, 1), 4), np.float32) if pts is None else pts
-        results = np.zeros(max(n, 1), EPI_RESULT_DTYPE) if results is None else results
-        mask = np.zeros(max(cap, 1), np.uint8) if mask is None else mask
-        assert out.dtype == DMATCH_DTYPE and out.flags["C_CONTIGUOUS"] and len(out) >= cap
-        assert pts.dtype == np.float32 and pts.flags["C_CONTIGUOUS"] and pts.shape[1:] == (4,) and len(pts) >= cap
-        assert results.dtype == EPI_RESULT_DTYPE and len(results) >= n and mask.dtype == np.uint8 and len(mask) >= cap
-        offs = np.zeros(n + 1, np.uintp)
-        self.last_offsets = offs
-        _check(self._lib.lcm_epi_db_verify_pairs(self._h, _ptr(pr), n, ratio, C.byref(ep), results.ctypes.data_as(_vp),
-                                                 out.ctypes.data_as(_vp), pts.ctypes.data_as(_vp), mask.ctypes.data_as(_vp), cap,
-                                                 offs.ctypes.data_as(_vp)))
-        total = int(offs[n])
-        return results[:n], out[:total], pts[:total], mask[:total], offs
+        return self._db_pairs_call(self._lib.lcm_epi_db_verify_pairs, (C.byref(ep),), pairs, ratio, cap, epi=True, out=out, pts=pts,
+                                   results=results, mask=mask)
 
     def epi_db_detect_loops(self, curr: int, loop_gap: int, ep: EpiParams, query=None, query_pts=None, skip=None,
                             ratio: Optional[float] = None, min_rows: Optional[int] = None, min_matches: Optional[int] = None,
                             cand_cap: Optional[int] = None, cap: Optional[int] = None):
         """l2_db_detect_loops_points plus the verification of every candidate: (candidates, pairs scored, EPI_RESULT_DTYPE
         [n_candidates], DMATCH_DTYPE[total], float32[total, 4], uint8[total] mask, offsets[n_candidates + 1])."""
-        rpp, _rp, sk, cand_cap, cands = self._l2_db_search_args(skip, ratio, min_rows, min_matches, cand_cap, None)
-        q = None if query is None else _sift_rows(query)
-        nq = 0 if q is None else q.shape[0]
-        qp = None if q is None else (q if q.size else np.zeros((1, SIFT_BYTES), np.uint8)).ctypes.data_as(_vp)
-        kp = None if (q is None or query_pts is None) else self._kp(query_pts, nq)
-        kpp = None if kp is None else (kp if kp.size else np.zeros((1, 2), np.float32)).ctypes.data_as(_vp)
-        if cap is None:
-            rows_q = nq if q is not None else (self.l2_db_rows(curr) if 0 <= curr < self.l2_db_size() else 0)
-            cap = rows_q * max(min(cand_cap, self.l2_db_size()), 1)
-        out = np.zeros(max(cap, 1), DMATCH_DTYPE)
-        pts = np.zeros((max(cap, 1), 4), np.float32)
-        mask = np.zeros(max(cap, 1), np.uint8)
-        results = np.zeros(max(cand_cap, 1), EPI_RESULT_DTYPE)
-        offs = np.zeros(cand_cap + 1, np.uintp)
-        n, npairs = C.c_size_t(0), C.c_size_t(0)
-        self.last_offsets, self.last_n_cands = offs, n
-        _check(self._lib.lcm_epi_db_detect_loops(self._h, curr, qp, kpp, nq, _ptr(sk), loop_gap, rpp, C.byref(ep),
-                                                 cands.ctypes.data_as(_vp), cand_cap, C.byref(n), C.byref(npairs),
-                                                 results.ctypes.data_as(_vp), out.ctypes.data_as(_vp), pts.ctypes.data_as(_vp),
-                                                 mask.ctypes.data_as(_vp), cap, offs.ctypes.data_as(_vp)))
-        total = int(offs[n.value])
-        return cands[: n.value], npairs.value, results[: n.value], out[:total], pts[:total], mask[:total], offs[: n.value + 1]
+        return self._db_detect_call(self._lib.lcm_epi_db_detect_loops, (C.byref(ep),), curr, loop_gap, query, query_pts, skip, ratio,
+                                    min_rows, min_matches, cand_cap, cap, epi=True)
 
     # -- loop verification, second step: the RANSAC's best hypotheses refitted on their inliers (lcm_lo_*) --
     def lo_verify_pairs(self, pts, offsets, ep: EpiParams, lp: Optional[LoParams] = None, want_mask: bool = True):
@@ -1094,35 +1092,9 @@ class Matcher:
         """pose_db_verify_pairs with the local optimisation between the RANSAC and the pose recovery: (EPI_RESULT_DTYPE[n],
         LO_INFO_DTYPE[n], POSE_RESULT_DTYPE[n], DMATCH_DTYPE[total], float32[total, 4], uint8[total] inlier mask, uint8[total]
         pose mask, offsets[n + 1]).  out / pts / results / info / mask / pose_results / pose_mask: the caller's buffers."""
-        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-        n = pr.shape[0]
-        if cap is None:
-            if out is not None:
-                cap = len(out)
-            else:
-                size = self.l2_db_size()
-                cap = sum(self.l2_db_rows(int(q)) for q in pr[:, 0] if 0 <= q < size)
-        out = np.zeros(max(cap, 1), DMATCH_DTYPE) if out is None else out
-        pts = np.zeros((max(cap, 1), 4), np.float32) if pts is None else pts
-        results = np.zeros(max(n, 1), EPI_RESULT_DTYPE) if results is None else results
-        info = np.zeros(max(n, 1), LO_INFO_DTYPE) if info is None else info
-        mask = np.zeros(max(cap, 1), np.uint8) if mask is None else mask
-        pose_results = np.zeros(max(n, 1), POSE_RESULT_DTYPE) if pose_results is None else pose_results
-        pose_mask = np.zeros(max(cap, 1), np.uint8) if pose_mask is None else pose_mask
-        assert out.dtype == DMATCH_DTYPE and out.flags["C_CONTIGUOUS"] and len(out) >= cap
-        assert pts.dtype == np.float32 and pts.flags["C_CONTIGUOUS"] and pts.shape[1:] == (4,) and len(pts) >= cap
-        assert results.dtype == EPI_RESULT_DTYPE and len(results) >= n and mask.dtype == np.uint8 and len(mask) >= cap
-        assert info.dtype == LO_INFO_DTYPE and len(info) >= n
-        assert pose_results.dtype == POSE_RESULT_DTYPE and len(pose_results) >= n and pose_mask.dtype == np.uint8 and len(pose_mask) >= cap
-        offs = np.zeros(n + 1, np.uintp)
-        self.last_offsets = offs
-        _check(self._lib.lcm_lo_db_verify_pairs(self._h, _ptr(pr), n, ratio, C.byref(ep), None if lp is None else C.byref(lp),
-                                                None if pp is None else C.byref(pp), results.ctypes.data_as(_vp),
-                                                info.ctypes.data_as(_vp), pose_results.ctypes.data_as(_vp), out.ctypes.data_as(_vp),
-                                                pts.ctypes.data_as(_vp), mask.ctypes.data_as(_vp), pose_mask.ctypes.data_as(_vp), cap,
-                                                offs.ctypes.data_as(_vp)))
-        total = int(offs[n])
-        return results[:n], info[:n], pose_results[:n], out[:total], pts[:total], mask[:total], pose_mask[:total], offs
+        return self._db_pairs_call(self._lib.lcm_lo_db_verify_pairs, (C.byref(ep), _ref(lp), _ref(pp)), pairs, ratio, cap, epi=True, lo=True,
+                                   pose=True, out=out, pts=pts, results=results, info=info, mask=mask, pose_results=pose_results,
+                                   pose_mask=pose_mask)
 
     def lo_db_detect_loops(self, curr: int, loop_gap: int, ep: EpiParams, lp: Optional[LoParams] = None,
                            pp: Optional[PoseParams] = None, floor_inliers: int = -1, query=None, query_pts=None, skip=None,
@@ -1131,35 +1103,9 @@ class Matcher:
         """pose_db_detect_loops with the local optimisation between the RANSAC and the pose recovery: (candidates, pairs scored,
         EPI_RESULT_DTYPE[n_candidates], LO_INFO_DTYPE[n_candidates], POSE_RESULT_DTYPE[n_candidates], DMATCH_DTYPE[total],
         float32[total, 4], uint8[total] inlier mask, uint8[total] pose mask, offsets[n_candidates + 1], best)."""
-        rpp, _rp, sk, cand_cap, cands = self._l2_db_search_args(skip, ratio, min_rows, min_matches, cand_cap, None)
-        q = None if query is None else _sift_rows(query)
-        nq = 0 if q is None else q.shape[0]
-        qp = None if q is None else (q if q.size else np.zeros((1, SIFT_BYTES), np.uint8)).ctypes.data_as(_vp)
-        kp = None if (q is None or query_pts is None) else self._kp(query_pts, nq)
-        kpp = None if kp is None else (kp if kp.size else np.zeros((1, 2), np.float32)).ctypes.data_as(_vp)
-        if cap is None:
-            rows_q = nq if q is not None else (self.l2_db_rows(curr) if 0 <= curr < self.l2_db_size() else 0)
-            cap = rows_q * max(min(cand_cap, self.l2_db_size()), 1)
-        out = np.zeros(max(cap, 1), DMATCH_DTYPE)
-        pts = np.zeros((max(cap, 1), 4), np.float32)
-        mask = np.zeros(max(cap, 1), np.uint8)
-        pose_mask = np.zeros(max(cap, 1), np.uint8)
-        results = np.zeros(max(cand_cap, 1), EPI_RESULT_DTYPE)
-        info = np.zeros(max(cand_cap, 1), LO_INFO_DTYPE)
-        pose_results = np.zeros(max(cand_cap, 1), POSE_RESULT_DTYPE)
-        offs = np.zeros(cand_cap + 1, np.uintp)
-        n, npairs, best = C.c_size_t(0), C.c_size_t(0), C.c_int32(-1)
-        self.last_offsets, self.last_n_cands = offs, n
-        _check(self._lib.lcm_lo_db_detect_loops(self._h, curr, qp, kpp, nq, _ptr(sk), loop_gap, rpp, C.byref(ep),
-                                                None if lp is None else C.byref(lp), None if pp is None else C.byref(pp),
-                                                cands.ctypes.data_as(_vp), cand_cap, C.byref(n), C.byref(npairs),
-                                                results.ctypes.data_as(_vp), info.ctypes.data_as(_vp),
-                                                pose_results.ctypes.data_as(_vp), out.ctypes.data_as(_vp), pts.ctypes.data_as(_vp),
-                                                mask.ctypes.data_as(_vp), pose_mask.ctypes.data_as(_vp), cap,
-                                                offs.ctypes.data_as(_vp), floor_inliers, C.byref(best)))
-        total = int(offs[n.value])
-        return (cands[: n.value], npairs.value, results[: n.value], info[: n.value], pose_results[: n.value], out[:total],
-                pts[:total], mask[:total], pose_mask[:total], offs[: n.value + 1], best.value)
+        return self._db_detect_call(self._lib.lcm_lo_db_detect_loops, (C.byref(ep), _ref(lp), _ref(pp)), curr, loop_gap, query, query_pts,
+                                    skip, ratio, min_rows, min_matches, cand_cap, cap, floor_inliers=floor_inliers, epi=True, lo=True,
+                                    pose=True)
 
     # -- the loop's relative pose on the device and the best loop (lcm_pose_*) --
     def pose_recover_pairs(self, pts, offsets, E, ep: EpiParams, pp: Optional[PoseParams] = None, mask_in=None,
@@ -1198,32 +1144,8 @@ class Matcher:
         """epi_db_verify_pairs followed by the pose recovery on the device's own records, matrices and mask:
         (EPI_RESULT_DTYPE[n], POSE_RESULT_DTYPE[n], DMATCH_DTYPE[total], float32[total, 4], uint8[total] inlier mask,
         uint8[total] pose mask, offsets[n + 1]).  out / pts / results / mask / pose_results / pose_mask: the caller's buffers."""
-        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-        n = pr.shape[0]
-        if cap is None:
-            if out is not None:
-                cap = len(out)
-            else:
-                size = self.l2_db_size()
-                cap = sum(self.l2_db_rows(int(q)) for q in pr[:, 0] if 0 <= q < size)
-        out = np.zeros(max(cap, 1), DMATCH_DTYPE) if out is None else out
-        pts = np.zeros((max(cap, 1), 4), np.float32) if pts is None else pts
-        results = np.zeros(max(n, 1), EPI_RESULT_DTYPE) if results is None else results
-        mask = np.zeros(max(cap, 1), np.uint8) if mask is None else mask
-        pose_results = np.zeros(max(n, 1), POSE_RESULT_DTYPE) if pose_results is None else pose_results
-        pose_mask = np.zeros(max(cap, 1), np.uint8) if pose_mask is None else pose_mask
-        assert out.dtype == DMATCH_DTYPE and out.flags["C_CONTIGUOUS"] and len(out) >= cap
-        assert pts.dtype == np.float32 and pts.flags["C_CONTIGUOUS"] and pts.shape[1:] == (4,) and len(pts) >= cap
-        assert results.dtype == EPI_RESULT_DTYPE and len(results) >= n and mask.dtype == np.uint8 and len(mask) >= cap
-        assert pose_results.dtype == POSE_RESULT_DTYPE and len(pose_results) >= n and pose_mask.dtype == np.uint8 and len(pose_mask) >= cap
-        offs = np.zeros(n + 1, np.uintp)
-        self.last_offsets = offs
-        _check(self._lib.lcm_pose_db_verify_pairs(self._h, _ptr(pr), n, ratio, C.byref(ep), None if pp is None else C.byref(pp),
-                                                  results.ctypes.data_as(_vp), pose_results.ctypes.data_as(_vp),
-                                                  out.ctypes.data_as(_vp), pts.ctypes.data_as(_vp), mask.ctypes.data_as(_vp),
-                                                  pose_mask.ctypes.data_as(_vp), cap, offs.ctypes.data_as(_vp)))
-        total = int(offs[n])
-        return results[:n], pose_results[:n], out[:total], pts[:total], mask[:total], pose_mask[:total], offs
+        return self._db_pairs_call(self._lib.lcm_pose_db_verify_pairs, (C.byref(ep), _ref(pp)), pairs, ratio, cap, epi=True, pose=True,
+                                   out=out, pts=pts, results=results, mask=mask, pose_results=pose_results, pose_mask=pose_mask)
 
     def pose_db_detect_loops(self, curr: int, loop_gap: int, ep: EpiParams, pp: Optional[PoseParams] = None, floor_inliers: int = -1,
                              query=None, query_pts=None, skip=None, ratio: Optional[float] = None, min_rows: Optional[int] = None,
@@ -1232,33 +1154,8 @@ class Matcher:
         scored, EPI_RESULT_DTYPE[n_candidates], POSE_RESULT_DTYPE[n_candidates], DMATCH_DTYPE[total], float32[total, 4],
         uint8[total] inlier mask, uint8[total] pose mask, offsets[n_candidates + 1], best).  best: the index of the candidate
         the reference's globalBest* update ends at when it starts from floor_inliers, or -1."""
-        rpp, _rp, sk, cand_cap, cands = self._l2_db_search_args(skip, ratio, min_rows, min_matches, cand_cap, None)
-        q = None if query is None else _sift_rows(query)
-        nq = 0 if q is None else q.shape[0]
-        qp = None if q is None else (q if q.size else np.zeros((1, SIFT_BYTES), np.uint8)).ctypes.data_as(_vp)
-        kp = None if (q is None or query_pts is None) else self._kp(query_pts, nq)
-        kpp = None if kp is None else (kp if kp.size else np.zeros((1, 2), np.float32)).ctypes.data_as(_vp)
-        if cap is None:
-            rows_q = nq if q is not None else (self.l2_db_rows(curr) if 0 <= curr < self.l2_db_size() else 0)
-            cap = rows_q * max(min(cand_cap, self.l2_db_size()), 1)
-        out = np.zeros(max(cap, 1), DMATCH_DTYPE)
-        pts = np.zeros((max(cap, 1), 4), np.float32)
-        mask = np.zeros(max(cap, 1), np.uint8)
-        pose_mask = np.zeros(max(cap, 1), np.uint8)
-        results = np.zeros(max(cand_cap, 1), EPI_RESULT_DTYPE)
-        pose_results = np.zeros(max(cand_cap, 1), POSE_RESULT_DTYPE)
-        offs = np.zeros(cand_cap + 1, np.uintp)
-        n, npairs, best = C.c_size_t(0), C.c_size_t(0), C.c_int32(-1)
-        self.last_offsets, self.last_n_cands = offs, n
-        _check(self._lib.lcm_pose_db_detect_loops(self._h, curr, qp, kpp, nq, _ptr(sk), loop_gap, rpp, C.byref(ep),
-                                                  None if pp is None else C.byref(pp), cands.ctypes.data_as(_vp), cand_cap,
-                                                  C.byref(n), C.byref(npairs), results.ctypes.data_as(_vp),
-                                                  pose_results.ctypes.data_as(_vp), out.ctypes.data_as(_vp), pts.ctypes.data_as(_vp),
-                                                  mask.ctypes.data_as(_vp), pose_mask.ctypes.data_as(_vp), cap,
-                                                  offs.ctypes.data_as(_vp), floor_inliers, C.byref(best)))
-        total = int(offs[n.value])
-        return (cands[: n.value], npairs.value, results[: n.value], pose_results[: n.value], out[:total], pts[:total], mask[:total],
-                pose_mask[:total], offs[: n.value + 1], best.value)
+        return self._db_detect_call(self._lib.lcm_pose_db_detect_loops, (C.byref(ep), _ref(pp)), curr, loop_gap, query, query_pts, skip,
+                                    ratio, min_rows, min_matches, cand_cap, cap, floor_inliers=floor_inliers, epi=True, pose=True)
 
     @staticmethod
     def pose_best(epi_results, pose_results, ep: EpiParams, pp: Optional[PoseParams] = None, floor_inliers: int = -1) -> int:

@@ -1,11 +1,11 @@
 // lcm_epi.cpp — the host side of the essential-matrix RANSAC (include/lcm.h, lcm_epi_*): src/main.cpp:1395-1403 over point
-// lists.  The kernels are lcm_epi.hip's, the arithmetic lcm_epi_device.h's, the pure checks lcm_epi_host.h's.  The store's
-// forms (lcm_epi_db_*) live in lcm_l2.cpp beside the list kernels whose records they read; they enqueue through epi_enqueue.
+// lists.  The kernels are lcm_epi.hip's, the arithmetic lcm_epi_device.h's, the pure checks lcm_epi_host.h's.  The stage runs
+// through lcm_verify.cpp's pipeline: lcm_epi_verify_pairs here, the store's forms (lcm_epi_db_*) in lcm_l2.cpp beside the list
+// kernels whose records they read.
 // Part of liblcm_hip.so's host side; shared state and helpers: lcm_internal.h.
 #include "lcm_internal.h"
 
 #include "lcm_epi_device.h"
-#include "lcm_epi_host.h"
 
 static_assert(sizeof(lcm_epi_result) == 88 && sizeof(lcm::EpiResult) == 88 && sizeof(lcm_epi_params) == 64, "record sizes");
 static_assert(offsetof(lcm_epi_result, n_points) == 72 && offsetof(lcm::EpiResult, n_points) == 72 &&
@@ -52,10 +52,9 @@ int epi_enqueue(lcm_handle* h, const uint4* d_pts, const uint64_t* d_off, size_t
     if (e == hipSuccess) e = launch_epi_score(a, (uint32_t)n_pairs, h->stream);
     if (e == hipSuccess) e = launch_epi_mask(a, (uint32_t)n_pairs, max_n, h->stream);
     if (e != hipSuccess) return fail(LCM_ERR_HIP, "RANSAC kernels: launch failed: %s", hipGetErrorString(e));
-    uint32_t lim = 1;
-    e = grid_y_limit(&lim);
-    if (e != hipSuccess) return fail(LCM_ERR_HIP, "grid limit: %s", hipGetErrorString(e));
-    *launches = 3u * (uint32_t)((n_pairs + lim - 1) / lim);
+    uint32_t slices = 0;
+    rc = pair_slices(n_pairs, &slices); if (rc) return rc;
+    *launches = 3u * slices;
     return LCM_OK;
 }
 
@@ -79,33 +78,6 @@ int epi_upload_points(lcm_handle* h, const lcm_point_pair* pts, const size_t* of
 
 namespace {
 using lcm::epi_upload_points;
-
-int epi_verify_pairs_impl(lcm_handle* h, const lcm_point_pair* pts, const size_t* offsets, int n_pairs, const lcm_epi_params* ep,
-                          lcm_epi_result* results, uint8_t* mask) {
-    if (!h) return fail(LCM_ERR_INVALID_ARG, "bad argument");
-    int rc = lcm::epi_params_checked(ep); if (rc) return rc;
-    size_t total = 0;
-    uint32_t max_n = 0;
-    bool capacity = false;
-    if (const char* what = lcm::epi_offsets_problem(offsets, n_pairs, lcm::EPI_MAX_POINTS, &total, &max_n, &capacity))
-        return fail(capacity ? LCM_ERR_CAPACITY : LCM_ERR_INVALID_ARG, "%s", what);
-    if ((n_pairs > 0 && !results) || (total > 0 && !pts)) return fail(LCM_ERR_INVALID_ARG, "NULL buffer");
-    if (n_pairs == 0) return LCM_OK;
-    rc = set_device(h); if (rc) return rc;
-    const size_t P = (size_t)n_pairs;
-    rc = epi_upload_points(h, pts, offsets, P, total); if (rc) return rc;
-    uint32_t launches = 0;
-    HIP_TRY(hipEventRecord(h->ev_start, h->stream));
-    rc = lcm::epi_enqueue(h, h->epi.d_pts, h->epi.d_off, P, max_n, total, *ep, &launches); if (rc) return rc;
-    HIP_TRY(hipEventRecord(h->ev_stop, h->stream));
-    h->info_pending = true;
-    h->info.workgroups = (uint32_t)(P * (size_t)((ep->iters + 255) / 256)); h->info.route = LCM_ROUTE_PLAIN; h->info.launches = launches;
-    h->info.pairs = P; h->info.distances = (uint64_t)total * (uint64_t)ep->iters;
-    h->info.algo_bytes = total * 17 + P * ((uint64_t)ep->iters * 104 + sizeof(lcm_epi_result));
-    rc = lcm::epi_download(h, P, total, results, mask); if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return LCM_OK;
-}
 
 // what the two seams check alike; one pair of n records at h->epi.d_pts / d_off on return
 int seam_pair(lcm_handle* h, const lcm_point_pair* pts, int n, const lcm_epi_params* ep) {
@@ -163,7 +135,10 @@ void lcm_epi_params_default(lcm_epi_params* p) { if (p) lcm::epi_params_default(
 int lcm_epi_loop_test(const lcm_epi_result* r, const lcm_epi_params* ep) { return lcm::epi_loop_test(r, ep); }
 int lcm_epi_verify_pairs(lcm_handle* h, const lcm_point_pair* pts, const size_t* offsets, int n_pairs, const lcm_epi_params* ep,
                          lcm_epi_result* results, uint8_t* mask) {
-    return guarded([&] { return epi_verify_pairs_impl(h, pts, offsets, n_pairs, ep, results, mask); });
+    return guarded([&] {
+        lcm::VerifyPlan plan{ep, false, false, results, mask};
+        return lcm::verify_pairs(h, pts, offsets, n_pairs, &plan, nullptr);
+    });
 }
 int lcm_epi_hypotheses(lcm_handle* h, const lcm_point_pair* pts, int n, uint32_t pair_index, const lcm_epi_params* ep, int32_t* samples,
                        double* E) {

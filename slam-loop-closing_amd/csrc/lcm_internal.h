@@ -10,6 +10,7 @@
 //   lcm_epi.cpp        essential-matrix RANSAC over the loop candidates' correspondences (lcm_epi_*)
 //   lcm_pose.cpp       relative pose of the verified candidates and the best loop (lcm_pose_*)
 //   lcm_lo.cpp         local optimisation of the RANSAC's best hypotheses (lcm_lo_*)
+//   lcm_verify.cpp     the three as one staged pipeline over a VerifyPlan (lcm_verify_host.h); the store's and the host-list forms
 // Not installed; the public surface is include/lcm.h.
 #pragma once
 #include "../../include/lcm.h"
@@ -27,6 +28,7 @@
 #include <vector>
 
 #include "lcm_kernels.h"
+#include "lcm_verify_host.h"
 
 namespace lcm {
 // last error message of the calling thread (lcm_last_error()); `fail` formats it and returns `code`
@@ -417,38 +419,46 @@ int stored_src(lcm_handle* h, int frame_id, RowSrc* out, int* n_kp);    // devic
 // frames train_ids; else the stored pairs): job_of[p] = pair p's job, -1 when a side is empty.
 int batch_jobs(lcm_handle* h, const uint8_t* q_host, int nq_host, const lcm_pair_ref* pairs, const int32_t* train_ids,
                int n_pairs, std::vector<PairJob>& jobs, std::vector<int>& job_of, size_t* stage_bytes);
-// ---- lcm_epi.cpp: the RANSAC behind lcm_epi_*; lcm_l2.cpp runs it on the list kernel's point records
-// ep checked (LCM_ERR_INVALID_ARG and the message otherwise)
+// ---- lcm_epi.cpp, lcm_lo.cpp, lcm_pose.cpp: the stages of the loop verification.  Every *_enqueue works on h's stream over
+// n_pairs pairs whose records d_pts[d_off[p] .. d_off[p + 1]) are on the device (max_n = the longest pair, total =
+// d_off[n_pairs]), sets *launches to the kernel launches it made and does not wait; every *_download enqueues the copies of
+// the last *_enqueue's records to the host (the caller waits; a mask may be NULL).
+// ep checked (LCM_ERR_INVALID_ARG and the message otherwise); lp / pp checked into *out, the defaults for NULL
 int epi_params_checked(const lcm_epi_params* ep);
-// Enqueues k_epi_solve, k_epi_score and k_epi_mask on h's stream over n_pairs pairs whose records d_pts[d_off[p] .. d_off[p + 1])
-// are on the device (max_n = the longest pair, total = d_off[n_pairs]); results -> h->epi.d_res, mask -> h->epi.d_mask.
-// *launches = kernel launches made.  No host wait.  want_counts: every hypothesis's inlier count -> h->epi.d_counts as well
-// (what lo_enqueue reads).
+int lo_params_checked(const lcm_lo_params* lp, lcm_lo_params* out);
+int pose_params_checked(const lcm_pose_params* pp, lcm_pose_params* out);
+// k_epi_solve, k_epi_score, k_epi_mask: results -> h->epi.d_res, mask -> h->epi.d_mask; want_counts: every hypothesis's inlier
+// count -> h->epi.d_counts as well (what lo_enqueue reads)
 int epi_enqueue(lcm_handle* h, const uint4* d_pts, const uint64_t* d_off, size_t n_pairs, uint32_t max_n, size_t total,
                 const lcm_epi_params& ep, uint32_t* launches, bool want_counts = false);
-// Copies of the last epi_enqueue's records to the host, enqueued (the caller waits); mask may be NULL
 int epi_download(lcm_handle* h, size_t n_pairs, size_t total, lcm_epi_result* results, uint8_t* mask);
 // A host call's records and offsets -> h->epi.d_pts / d_off, enqueued (the sources are pageable: the caller waits)
 int epi_upload_points(lcm_handle* h, const lcm_point_pair* pts, const size_t* offsets, size_t n_pairs, size_t total);
-// ---- lcm_lo.cpp: the local optimisation behind lcm_lo_*; lcm_l2.cpp runs it between the RANSAC and the pose recovery
-// NULL or checked parameters -> *out (the defaults for NULL)
-int lo_params_checked(const lcm_lo_params* lp, lcm_lo_params* out);
-// Enqueues k_lo_select and k_lo_refine on h's stream behind an epi_enqueue(..., want_counts = true) over the same pairs: they
-// read h->epi.d_E / d_counts and rewrite h->epi.d_res / d_mask where a refit is better; info -> h->lo.d_info.  No host wait.
+// k_lo_select, k_lo_refine behind an epi_enqueue(..., want_counts = true) over the same pairs: they read h->epi.d_E / d_counts
+// and rewrite h->epi.d_res / d_mask where a refit is better; info -> h->lo.d_info
 int lo_enqueue(lcm_handle* h, const uint4* d_pts, const uint64_t* d_off, size_t n_pairs, const lcm_epi_params& ep,
                const lcm_lo_params& lp, uint32_t* launches);
-// Copy of the last lo_enqueue's info records to the host, enqueued (the caller waits)
 int lo_download(lcm_handle* h, size_t n_pairs, lcm_lo_info* info);
-// ---- lcm_pose.cpp: the pose recovery behind lcm_pose_*; lcm_l2.cpp runs it on the RANSAC's records
-// pp checked (LCM_ERR_INVALID_ARG and the message otherwise); *out = pp's values, or the defaults for NULL
-int pose_params_checked(const lcm_pose_params* pp, lcm_pose_params* out);
-// Enqueues k_pose_recover on h's stream over n_pairs pairs whose records d_pts[d_off[p] .. d_off[p + 1]) are on the device
-// (total = d_off[n_pairs]), pair p's matrix at d_E[p * e_stride ..], d_mask_in (NULL: all) one byte per record; results ->
-// h->pose.d_res, mask -> h->pose.d_mask.  *launches = kernel launches made.  No host wait.
+// k_pose_recover: pair p's matrix at d_E[p * e_stride ..], d_mask_in (NULL: all) one byte per record; results -> h->pose.d_res,
+// mask -> h->pose.d_mask
 int pose_enqueue(lcm_handle* h, const uint4* d_pts, const uint64_t* d_off, size_t n_pairs, size_t total, const double* d_E,
                  uint32_t e_stride, const uint8_t* d_mask_in, const lcm_epi_params& ep, const lcm_pose_params& pp, uint32_t* launches);
-// Copies of the last pose_enqueue's records to the host, enqueued (the caller waits); mask may be NULL
 int pose_download(lcm_handle* h, size_t n_pairs, size_t total, lcm_pose_result* results, uint8_t* mask);
+// ---- lcm_verify.cpp: the stages as one pipeline over a VerifyPlan (lcm_verify_host.h); lcm_l2.cpp runs it on the list kernel's
+// point records
+// *slices = launches of a kernel whose grid's y is the pair: ceil(n_pairs / grid_y_limit())
+int pair_slices(size_t n_pairs, uint32_t* slices);
+// A host call's offsets walked (epi_offsets_problem): LCM_ERR_CAPACITY for an over-long pair, LCM_ERR_INVALID_ARG otherwise
+int offsets_checked(const size_t* offsets, int n_pairs, size_t* total, uint32_t* max_n);
+// The parameters of the plan's stages that are on, checked into the plan: the pose's, then the optimisation's
+int verify_params_checked(VerifyPlan* plan, const lcm_lo_params* lp, const lcm_pose_params* pp);
+// epi_enqueue, then lo_enqueue and pose_enqueue (on the device's results[].E and mask) where the plan wants them; *launches =
+// their sum.  verify_download: the same stages' records to the plan's buffers, enqueued.
+int verify_enqueue(lcm_handle* h, const VerifyPlan& plan, const uint4* d_pts, const uint64_t* d_off, size_t n_pairs, uint32_t max_n,
+                   size_t total, uint32_t* launches);
+int verify_download(lcm_handle* h, const VerifyPlan& plan, size_t n_pairs, size_t total);
+// lcm_epi_verify_pairs / lcm_lo_verify_pairs: a plan without the pose stage over host point pairs; lp as the caller gave it
+int verify_pairs(lcm_handle* h, const lcm_point_pair* pts, const size_t* offsets, int n_pairs, VerifyPlan* plan, const lcm_lo_params* lp);
 }  // namespace lcm
 
 namespace {

@@ -6,14 +6,10 @@
 // only: lcm_l2_count.hip scores a pair's whole train matrix in one workgroup per query chunk and decides on the device, so
 // 8 bytes per pair come back.  The SIFT keyframe store (lcm_l2_db_*) keeps uploaded and packed matrices on the device and
 // searches them from tables that grow with the frames (lcm_l2_store.hip); its list calls can hand the point records straight to
-// the essential-matrix RANSAC (lcm_epi_db_*: store_lists enqueues lcm_epi.cpp's kernels) and on to the pose recovery
-// (lcm_pose_db_*: lcm_pose.cpp's kernel; the best loop is chosen on the host).  Part of liblcm_hip.so's host side (C ABI in include/lcm.h); shared state and helpers:
-// lcm_internal.h.
+// the loop verification (lcm_epi_db_*, lcm_lo_db_*, lcm_pose_db_*: store_lists runs the call's lcm::VerifyPlan through
+// lcm_verify.cpp's pipeline; the best loop is chosen on the host).  Part of liblcm_hip.so's host side (C ABI in include/lcm.h);
+// shared state and helpers: lcm_internal.h.
 #include "lcm_internal.h"
-
-#include "lcm_epi_host.h"
-#include "lcm_lo_host.h"
-#include "lcm_pose_host.h"
 
 #include <cmath>
 #include <limits>
@@ -26,6 +22,7 @@ static_assert(LCM_SIFT_BYTES == lcm::L2_ROW_BYTES, "row size");
 
 struct L2Pair { int q, t; };                // positions into the call's matrices, both sides non-empty
 using L2Store = lcm_handle::L2Store;        // the SIFT keyframe store, below
+using lcm::VerifyPlan;                      // the loop verification behind the store's list calls (lcm_verify.cpp)
 
 // What every k = 2 call refuses (lcm_knn.cpp's rule)
 int check_knn(const lcm_handle* h, double ratio) {
@@ -781,26 +778,15 @@ static_assert(sizeof(size_t) == sizeof(uint64_t) && sizeof(lcm_dmatch) == sizeof
 // staged in the free tail); live[job_of[p]] = pair p, -1 when a side is empty.  Score, fold, rescan, then the ratio test, the
 // ordered compaction and the gather on the device; offsets (8 bytes per pair) come back first and decide about `cap`, then
 // only the records do.  pts == NULL: no point pairs.
-// epi != NULL (with pts): the essential-matrix RANSAC (lcm_epi.hip) runs on the point records as soon as k_l2_emit has written
-// them, pair p of the call seeded with p; its kernels count into `launches` and into the aux events' span.
-// pp != NULL (checked): the pose recovery (lcm_pose.hip) follows k_epi_mask on the same records, the device's results[].E and
-// the device's mask; one more launch per slice, inside the same span.
-// lp != NULL (checked, with info): the local optimisation (lcm_lo.hip) runs between the two, on the RANSAC's hypotheses and
-// counts; it rewrites results[] and the mask where a refit is better, so the pose recovery reads the optimised ones.
-struct EpiWanted {
-    const lcm_epi_params* ep; lcm_epi_result* results; uint8_t* mask;
-    const lcm_pose_params* pp = nullptr; lcm_pose_result* pose_results = nullptr; uint8_t* pose_mask = nullptr;
-    const lcm_lo_params* lp = nullptr; lcm_lo_info* info = nullptr;
-};
-
+// plan != NULL (checked, with pts): the plan's stages (lcm_verify.cpp: the RANSAC, then the local optimisation and the pose
+// recovery where wanted) run on the point records as soon as k_l2_emit has written them, pair p of the call seeded with p;
+// their kernels count into `launches` and into the aux events' span.
 int store_lists(lcm_handle* h, const int* rows, int n_frames, const std::vector<L2Pair>& live, const std::vector<int>& job_of,
-                double ratio, lcm_dmatch* out, lcm_point_pair* pts, size_t cap, size_t* offsets, const EpiWanted* epi = nullptr) {
+                double ratio, lcm_dmatch* out, lcm_point_pair* pts, size_t cap, size_t* offsets, const VerifyPlan* plan = nullptr) {
     const size_t n_pairs = job_of.size();
     if (live.empty()) {
         std::fill(offsets, offsets + n_pairs + 1, (size_t)0);
-        if (epi) lcm::epi_empty_results(epi->results, n_pairs);
-        if (epi && epi->pp) lcm::pose_empty_results(epi->pose_results, n_pairs);
-        if (epi && epi->lp) lcm::lo_empty_info(epi->info, n_pairs);
+        if (plan) lcm::verify_empty(*plan, n_pairs);
         return LCM_OK;
     }
     L2Store& d = h->l2db;
@@ -825,12 +811,10 @@ int store_lists(lcm_handle* h, const int* rows, int n_frames, const std::vector<
     uint32_t* d_blocks = s.d_blocks + n_pairs + 1;
     HIP_TRY(hipMemcpyAsync(s.d_blocks, pair_block.data(), (n_pairs + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
     lcm::L2EmitArgs ea{s.d_fin, dv.d_jobs, d_blocks, nullptr, nullptr, nullptr, ratio, 0, 0};
-    uint32_t lim = 1;
-    hipError_t e = lcm::grid_y_limit(&lim);
-    if (e != hipSuccess) return fail(LCM_ERR_HIP, "grid limit: %s", hipGetErrorString(e));
-    const uint32_t slices = (uint32_t)((P + lim - 1) / lim);
+    uint32_t slices = 0;
+    rc = lcm::pair_slices(P, &slices); if (rc) return rc;
     HIP_TRY(hipEventRecord(h->ev_aux_start, h->stream));
-    e = lcm::launch_l2_emit_count(ea, (uint32_t)P, (uint32_t)dv.max_nq, h->stream);
+    hipError_t e = lcm::launch_l2_emit_count(ea, (uint32_t)P, (uint32_t)dv.max_nq, h->stream);
     if (e == hipSuccess) e = lcm::launch_block_scan(d_blocks, (uint32_t)dv.n_blocks, d_blocks + dv.n_blocks, h->stream);
     if (e == hipSuccess) e = lcm::launch_l2_emit_offsets(d_blocks, s.d_blocks, s.d_offsets, (uint32_t)(n_pairs + 1), h->stream);
     if (e != hipSuccess) return fail(LCM_ERR_HIP, "list count kernels: launch failed: %s", hipGetErrorString(e));
@@ -854,21 +838,11 @@ int store_lists(lcm_handle* h, const int* rows, int n_frames, const std::vector<
         if (e != hipSuccess) return fail(LCM_ERR_HIP, "list kernel launch failed: %s", hipGetErrorString(e));
         h->info.launches += slices;
     }
-    if (epi) {                                      // a pair's records are at most its query rows: they fit the packed key
+    if (plan) {                                     // a pair's records are at most its query rows: they fit the packed key
         uint32_t max_n = 0, launches = 0;
         for (size_t p = 0; p < n_pairs; ++p) max_n = std::max(max_n, (uint32_t)(offsets[p + 1] - offsets[p]));
-        rc = lcm::epi_enqueue(h, s.d_rec_pts, s.d_offsets, n_pairs, max_n, total, *epi->ep, &launches, epi->lp != nullptr); if (rc) return rc;
+        rc = lcm::verify_enqueue(h, *plan, s.d_rec_pts, s.d_offsets, n_pairs, max_n, total, &launches); if (rc) return rc;
         h->info.launches += launches;
-        if (epi->lp) {
-            rc = lcm::lo_enqueue(h, s.d_rec_pts, s.d_offsets, n_pairs, *epi->ep, *epi->lp, &launches); if (rc) return rc;
-            h->info.launches += launches;
-        }
-        if (epi->pp) {
-            static_assert(sizeof(lcm_epi_result) == 11 * sizeof(double) && offsetof(lcm_epi_result, E) == 0, "results[].E as a matrix array");
-            rc = lcm::pose_enqueue(h, s.d_rec_pts, s.d_offsets, n_pairs, total, reinterpret_cast<const double*>(h->epi.d_res), 11,
-                                   h->epi.d_mask, *epi->ep, *epi->pp, &launches); if (rc) return rc;
-            h->info.launches += launches;
-        }
     }
     HIP_TRY(hipEventRecord(h->ev_aux_stop, h->stream));
     h->aux_pending = true;
@@ -876,11 +850,15 @@ int store_lists(lcm_handle* h, const int* rows, int n_frames, const std::vector<
         HIP_TRY(hipMemcpyAsync(out, s.d_rec, total * sizeof(uint4), hipMemcpyDeviceToHost, h->stream));
         if (pts) HIP_TRY(hipMemcpyAsync(pts, s.d_rec_pts, total * sizeof(uint4), hipMemcpyDeviceToHost, h->stream));
     }
-    if (epi) { rc = lcm::epi_download(h, n_pairs, total, epi->results, epi->mask); if (rc) return rc; }
-    if (epi && epi->lp) { rc = lcm::lo_download(h, n_pairs, epi->info); if (rc) return rc; }
-    if (epi && epi->pp) { rc = lcm::pose_download(h, n_pairs, total, epi->pose_results, epi->pose_mask); if (rc) return rc; }
-    if (total || epi) HIP_TRY(hipStreamSynchronize(h->stream));
+    if (plan) { rc = lcm::verify_download(h, *plan, n_pairs, total); if (rc) return rc; }
+    if (total || plan) HIP_TRY(hipStreamSynchronize(h->stream));
     return LCM_OK;
+}
+
+// what a list call with a plan refuses before anything else of its own: bad RANSAC parameters, a missing buffer
+int plan_checked(const VerifyPlan& plan, const lcm_point_pair* pts, size_t n_outputs) {
+    const char* what = lcm::verify_plan_problem(plan, pts, n_outputs);
+    return what ? fail(LCM_ERR_INVALID_ARG, "%s", what) : LCM_OK;
 }
 
 // `slot` is named by a list call that wants points: its rows must have theirs
@@ -890,14 +868,9 @@ int check_slot_pts(const L2Store& d, int slot) {
 }
 
 int l2_db_match_points_impl(lcm_handle* h, const lcm_pair_ref* slots, int n_pairs, double ratio, lcm_dmatch* out, lcm_point_pair* pts,
-                            size_t cap, size_t* offsets, const EpiWanted* epi = nullptr) {
+                            size_t cap, size_t* offsets, const VerifyPlan* plan = nullptr) {
     if (!h || n_pairs < 0 || !offsets || (n_pairs > 0 && !slots)) return fail(LCM_ERR_INVALID_ARG, "bad argument");
-    if (epi) {
-        const int rc = lcm::epi_params_checked(epi->ep); if (rc) return rc;
-        if (!pts || (n_pairs > 0 && !epi->results)) return fail(LCM_ERR_INVALID_ARG, "the verification needs pts and results");
-        if (epi->pp && n_pairs > 0 && !epi->pose_results) return fail(LCM_ERR_INVALID_ARG, "the pose recovery needs pose_results");
-        if (epi->lp && n_pairs > 0 && !epi->info) return fail(LCM_ERR_INVALID_ARG, "the optimisation needs info");
-    }
+    if (plan) { const int rc = plan_checked(*plan, pts, (size_t)n_pairs); if (rc) return rc; }
     offsets[0] = 0;
     int rc = check_knn(h, ratio); if (rc) return rc;
     const L2Store& d = h->l2db;
@@ -915,20 +888,17 @@ int l2_db_match_points_impl(lcm_handle* h, const lcm_pair_ref* slots, int n_pair
         job_of[(size_t)p] = (int)live.size();
         live.push_back(L2Pair{q, t});
     }
-    return store_lists(h, d.rows.data(), S, live, job_of, ratio, out, pts, cap, offsets, epi);
+    return store_lists(h, d.rows.data(), S, live, job_of, ratio, out, pts, cap, offsets, plan);
 }
 
 int l2_db_detect_loops_points_impl(lcm_handle* h, int curr, const uint8_t* query, const float* query_pts, int nq, const uint8_t* skip,
                                    int loop_gap, const lcm_ratio_loop_params* rp_in, lcm_loop_candidate* cands, size_t cand_cap,
                                    size_t* n_cands, size_t* n_pairs_out, lcm_dmatch* out, lcm_point_pair* pts, size_t cap, size_t* offsets,
-                                   const EpiWanted* epi = nullptr) {
+                                   const VerifyPlan* plan = nullptr) {
     if (!offsets) return fail(LCM_ERR_INVALID_ARG, "bad argument");
-    if (epi) {
+    if (plan) {
         if (!h) return fail(LCM_ERR_INVALID_ARG, "bad argument");
-        const int r = lcm::epi_params_checked(epi->ep); if (r) return r;
-        if (!pts || (cand_cap > 0 && !epi->results)) return fail(LCM_ERR_INVALID_ARG, "the verification needs pts and results");
-        if (epi->pp && cand_cap > 0 && !epi->pose_results) return fail(LCM_ERR_INVALID_ARG, "the pose recovery needs pose_results");
-        if (epi->lp && cand_cap > 0 && !epi->info) return fail(LCM_ERR_INVALID_ARG, "the optimisation needs info");
+        const int r = plan_checked(*plan, pts, cand_cap); if (r) return r;
     }
     lcm_ratio_loop_params rp;
     int rc = store_search_args(h, loop_gap, rp_in, n_cands, n_pairs_out, &rp); if (rc) return rc;
@@ -971,7 +941,7 @@ int l2_db_detect_loops_points_impl(lcm_handle* h, int curr, const uint8_t* query
             job_of[k] = (int)live.size();
             live.push_back(L2Pair{qpos, t});
         }
-        return store_lists(h, rows_ext.data(), S + 1, live, job_of, rp.ratio, out, pts, cap, offsets, epi);
+        return store_lists(h, rows_ext.data(), S + 1, live, job_of, rp.ratio, out, pts, cap, offsets, plan);
     };
     rc = body();
     if (query && nq > 0) {
@@ -979,6 +949,27 @@ int l2_db_detect_loops_points_impl(lcm_handle* h, int curr, const uint8_t* query
         if (e != hipSuccess && rc == LCM_OK) return fail(LCM_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
     }
     return rc;
+}
+
+// lcm_{pose,lo}_db_verify_pairs: the stages' parameters are checked before anything else (the pose's, then the optimisation's)
+int db_verify_pairs(lcm_handle* h, const lcm_pair_ref* slots, int n_pairs, double ratio, lcm_dmatch* out, lcm_point_pair* pts, size_t cap,
+                    size_t* offsets, VerifyPlan* plan, const lcm_lo_params* lp, const lcm_pose_params* pp) {
+    const int rc = lcm::verify_params_checked(plan, lp, pp); if (rc) return rc;
+    return l2_db_match_points_impl(h, slots, n_pairs, ratio, out, pts, cap, offsets, plan);
+}
+
+// lcm_{pose,lo}_db_detect_loops: the same, then `best`; the best loop among the verified candidates is chosen on the host
+int db_detect_best(lcm_handle* h, int curr, const uint8_t* query, const float* query_pts, int nq, const uint8_t* skip, int loop_gap,
+                   const lcm_ratio_loop_params* rp, lcm_loop_candidate* cands, size_t cand_cap, size_t* n_cands, size_t* n_pairs_out,
+                   lcm_dmatch* out, lcm_point_pair* pts, size_t cap, size_t* offsets, VerifyPlan* plan, const lcm_lo_params* lp,
+                   const lcm_pose_params* pp, int floor_inliers, int* best) {
+    int rc = lcm::verify_params_checked(plan, lp, pp); if (rc) return rc;
+    if (!best) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+    rc = l2_db_detect_loops_points_impl(h, curr, query, query_pts, nq, skip, loop_gap, rp, cands, cand_cap, n_cands, n_pairs_out, out, pts,
+                                        cap, offsets, plan);
+    if (rc) return rc;
+    *best = lcm::pose_best(plan->results, plan->pose_results, *n_cands, plan->ep, &plan->pp, floor_inliers);      // src/main.cpp:1403-1418
+    return LCM_OK;
 }
 
 int l2_ratio_test_device_impl(lcm_handle* h, const uint32_t* d1, const uint32_t* d2, size_t n, double ratio, uint8_t* pass) {
@@ -1098,7 +1089,7 @@ int lcm_l2_db_detect_loops_points(lcm_handle* h, int curr, const uint8_t* query,
 int lcm_epi_db_verify_pairs(lcm_handle* h, const lcm_pair_ref* slots, int n_pairs, double ratio, const lcm_epi_params* ep,
                             lcm_epi_result* results, lcm_dmatch* out, lcm_point_pair* pts, uint8_t* mask, size_t cap, size_t* offsets) {
     return guarded([&] {
-        const EpiWanted w{ep, results, mask};
+        const VerifyPlan w{ep, false, false, results, mask};
         return l2_db_match_points_impl(h, slots, n_pairs, ratio, out, pts, cap, offsets, &w);
     });
 }
@@ -1107,7 +1098,7 @@ int lcm_epi_db_detect_loops(lcm_handle* h, int curr, const uint8_t* query, const
                             size_t cand_cap, size_t* n_cands, size_t* n_pairs_out, lcm_epi_result* results, lcm_dmatch* out,
                             lcm_point_pair* pts, uint8_t* mask, size_t cap, size_t* offsets) {
     return guarded([&] {
-        const EpiWanted w{ep, results, mask};
+        const VerifyPlan w{ep, false, false, results, mask};
         return l2_db_detect_loops_points_impl(h, curr, query, query_pts, nq, skip, loop_gap, rp, cands, cand_cap, n_cands, n_pairs_out, out,
                                               pts, cap, offsets, &w);
     });
@@ -1116,10 +1107,8 @@ int lcm_pose_db_verify_pairs(lcm_handle* h, const lcm_pair_ref* slots, int n_pai
                              const lcm_pose_params* pp, lcm_epi_result* results, lcm_pose_result* pose_results, lcm_dmatch* out,
                              lcm_point_pair* pts, uint8_t* mask, uint8_t* pose_mask, size_t cap, size_t* offsets) {
     return guarded([&] {
-        lcm_pose_params ppv;
-        const int rc = lcm::pose_params_checked(pp, &ppv); if (rc) return rc;
-        const EpiWanted w{ep, results, mask, &ppv, pose_results, pose_mask};
-        return l2_db_match_points_impl(h, slots, n_pairs, ratio, out, pts, cap, offsets, &w);
+        VerifyPlan w{ep, false, true, results, mask, nullptr, pose_results, pose_mask};
+        return db_verify_pairs(h, slots, n_pairs, ratio, out, pts, cap, offsets, &w, nullptr, pp);
     });
 }
 int lcm_pose_db_detect_loops(lcm_handle* h, int curr, const uint8_t* query, const float* query_pts, int nq, const uint8_t* skip,
@@ -1127,16 +1116,10 @@ int lcm_pose_db_detect_loops(lcm_handle* h, int curr, const uint8_t* query, cons
                              lcm_loop_candidate* cands, size_t cand_cap, size_t* n_cands, size_t* n_pairs_out, lcm_epi_result* results,
                              lcm_pose_result* pose_results, lcm_dmatch* out, lcm_point_pair* pts, uint8_t* mask, uint8_t* pose_mask,
                              size_t cap, size_t* offsets, int floor_inliers, int* best) {
-    return guarded([&]() -> int {
-        lcm_pose_params ppv;
-        int rc = lcm::pose_params_checked(pp, &ppv); if (rc) return rc;
-        if (!best) return fail(LCM_ERR_INVALID_ARG, "bad argument");
-        const EpiWanted w{ep, results, mask, &ppv, pose_results, pose_mask};
-        rc = l2_db_detect_loops_points_impl(h, curr, query, query_pts, nq, skip, loop_gap, rp, cands, cand_cap, n_cands, n_pairs_out, out,
-                                            pts, cap, offsets, &w);
-        if (rc) return rc;
-        *best = lcm::pose_best(results, pose_results, *n_cands, ep, &ppv, floor_inliers);      // src/main.cpp:1403-1418, host only
-        return LCM_OK;
+    return guarded([&] {
+        VerifyPlan w{ep, false, true, results, mask, nullptr, pose_results, pose_mask};
+        return db_detect_best(h, curr, query, query_pts, nq, skip, loop_gap, rp, cands, cand_cap, n_cands, n_pairs_out, out, pts, cap, offsets,
+                              &w, nullptr, pp, floor_inliers, best);
     });
 }
 int lcm_lo_db_verify_pairs(lcm_handle* h, const lcm_pair_ref* slots, int n_pairs, double ratio, const lcm_epi_params* ep,
@@ -1144,12 +1127,8 @@ int lcm_lo_db_verify_pairs(lcm_handle* h, const lcm_pair_ref* slots, int n_pairs
                            lcm_pose_result* pose_results, lcm_dmatch* out, lcm_point_pair* pts, uint8_t* mask, uint8_t* pose_mask,
                            size_t cap, size_t* offsets) {
     return guarded([&] {
-        lcm_pose_params ppv;
-        lcm_lo_params lpv;
-        int rc = lcm::pose_params_checked(pp, &ppv); if (rc) return rc;
-        rc = lcm::lo_params_checked(lp, &lpv); if (rc) return rc;
-        const EpiWanted w{ep, results, mask, &ppv, pose_results, pose_mask, &lpv, info};
-        return l2_db_match_points_impl(h, slots, n_pairs, ratio, out, pts, cap, offsets, &w);
+        VerifyPlan w{ep, true, true, results, mask, info, pose_results, pose_mask};
+        return db_verify_pairs(h, slots, n_pairs, ratio, out, pts, cap, offsets, &w, lp, pp);
     });
 }
 int lcm_lo_db_detect_loops(lcm_handle* h, int curr, const uint8_t* query, const float* query_pts, int nq, const uint8_t* skip,
@@ -1158,18 +1137,10 @@ int lcm_lo_db_detect_loops(lcm_handle* h, int curr, const uint8_t* query, const 
                            lcm_epi_result* results, lcm_lo_info* info, lcm_pose_result* pose_results, lcm_dmatch* out,
                            lcm_point_pair* pts, uint8_t* mask, uint8_t* pose_mask, size_t cap, size_t* offsets, int floor_inliers,
                            int* best) {
-    return guarded([&]() -> int {
-        lcm_pose_params ppv;
-        lcm_lo_params lpv;
-        int rc = lcm::pose_params_checked(pp, &ppv); if (rc) return rc;
-        rc = lcm::lo_params_checked(lp, &lpv); if (rc) return rc;
-        if (!best) return fail(LCM_ERR_INVALID_ARG, "bad argument");
-        const EpiWanted w{ep, results, mask, &ppv, pose_results, pose_mask, &lpv, info};
-        rc = l2_db_detect_loops_points_impl(h, curr, query, query_pts, nq, skip, loop_gap, rp, cands, cand_cap, n_cands, n_pairs_out, out,
-                                            pts, cap, offsets, &w);
-        if (rc) return rc;
-        *best = lcm::pose_best(results, pose_results, *n_cands, ep, &ppv, floor_inliers);
-        return LCM_OK;
+    return guarded([&] {
+        VerifyPlan w{ep, true, true, results, mask, info, pose_results, pose_mask};
+        return db_detect_best(h, curr, query, query_pts, nq, skip, loop_gap, rp, cands, cand_cap, n_cands, n_pairs_out, out, pts, cap, offsets,
+                              &w, lp, pp, floor_inliers, best);
     });
 }
 int lcm_l2_ratio_test_device(lcm_handle* h, const uint32_t* d1, const uint32_t* d2, size_t n, double ratio, uint8_t* pass) {

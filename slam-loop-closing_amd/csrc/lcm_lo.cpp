@@ -1,13 +1,11 @@
 // lcm_lo.cpp — the host side of the RANSAC's local optimisation (include/lcm.h, lcm_lo_*): the refit of the 64 best
 // hypotheses on their inliers, between the RANSAC (lcm_epi.cpp) and the pose recovery (lcm_pose.cpp).  The kernels are
-// lcm_lo.hip's, the arithmetic lcm_lo_device.h's, the pure checks lcm_lo_host.h's.  The store's forms (lcm_lo_db_*) live in
-// lcm_l2.cpp beside the RANSAC whose records they rewrite; they enqueue through lo_enqueue.  Part of liblcm_hip.so's host
-// side; shared state and helpers: lcm_internal.h.
+// lcm_lo.hip's, the arithmetic lcm_lo_device.h's, the pure checks lcm_lo_host.h's.  The stage runs through lcm_verify.cpp's
+// pipeline: lcm_lo_verify_pairs here, the store's forms (lcm_lo_db_*) in lcm_l2.cpp.  Part of liblcm_hip.so's host side;
+// shared state and helpers: lcm_internal.h.
 #include "lcm_internal.h"
 
-#include "lcm_epi_host.h"
 #include "lcm_lo_device.h"
-#include "lcm_lo_host.h"
 
 static_assert(sizeof(lcm_lo_info) == 16 && sizeof(lcm::LoInfo) == 16 && sizeof(lcm_lo_params) == 96, "record sizes");
 static_assert(offsetof(lcm_lo_info, round) == 4 && offsetof(lcm::LoInfo, round) == 4 && offsetof(lcm_lo_info, status) == 12 &&
@@ -46,10 +44,9 @@ int lo_enqueue(lcm_handle* h, const uint4* d_pts, const uint64_t* d_off, size_t 
     hipError_t e = launch_lo_select(a, (uint32_t)n_pairs, h->stream);
     if (e == hipSuccess) e = launch_lo_refine(a, (uint32_t)n_pairs, h->stream);
     if (e != hipSuccess) return fail(LCM_ERR_HIP, "optimisation kernels: launch failed: %s", hipGetErrorString(e));
-    uint32_t lim = 1;
-    e = grid_y_limit(&lim);
-    if (e != hipSuccess) return fail(LCM_ERR_HIP, "grid limit: %s", hipGetErrorString(e));
-    *launches = 2u * (uint32_t)((n_pairs + lim - 1) / lim);
+    uint32_t slices = 0;
+    rc = pair_slices(n_pairs, &slices); if (rc) return rc;
+    *launches = 2u * slices;
     return LCM_OK;
 }
 
@@ -61,37 +58,6 @@ int lo_download(lcm_handle* h, size_t n_pairs, lcm_lo_info* info) {
 }  // namespace lcm
 
 namespace {
-
-int lo_verify_pairs_impl(lcm_handle* h, const lcm_point_pair* pts, const size_t* offsets, int n_pairs, const lcm_epi_params* ep,
-                         const lcm_lo_params* lp_in, lcm_epi_result* results, lcm_lo_info* info, uint8_t* mask) {
-    if (!h) return fail(LCM_ERR_INVALID_ARG, "bad argument");
-    int rc = lcm::epi_params_checked(ep); if (rc) return rc;
-    lcm_lo_params lp;
-    rc = lcm::lo_params_checked(lp_in, &lp); if (rc) return rc;
-    size_t total = 0;
-    uint32_t max_n = 0;
-    bool capacity = false;
-    if (const char* what = lcm::epi_offsets_problem(offsets, n_pairs, lcm::EPI_MAX_POINTS, &total, &max_n, &capacity))
-        return fail(capacity ? LCM_ERR_CAPACITY : LCM_ERR_INVALID_ARG, "%s", what);
-    if ((n_pairs > 0 && (!results || !info)) || (total > 0 && !pts)) return fail(LCM_ERR_INVALID_ARG, "NULL buffer");
-    if (n_pairs == 0) return LCM_OK;
-    rc = set_device(h); if (rc) return rc;
-    const size_t P = (size_t)n_pairs;
-    rc = lcm::epi_upload_points(h, pts, offsets, P, total); if (rc) return rc;
-    uint32_t launches = 0, more = 0;
-    HIP_TRY(hipEventRecord(h->ev_start, h->stream));
-    rc = lcm::epi_enqueue(h, h->epi.d_pts, h->epi.d_off, P, max_n, total, *ep, &launches, true); if (rc) return rc;
-    rc = lcm::lo_enqueue(h, h->epi.d_pts, h->epi.d_off, P, *ep, lp, &more); if (rc) return rc;
-    HIP_TRY(hipEventRecord(h->ev_stop, h->stream));
-    h->info_pending = true;
-    h->info.workgroups = (uint32_t)(P * (size_t)((ep->iters + 255) / 256)); h->info.route = LCM_ROUTE_PLAIN; h->info.launches = launches + more;
-    h->info.pairs = P; h->info.distances = (uint64_t)total * ((uint64_t)ep->iters + (uint64_t)lcm::LO_SEEDS * 4u * (uint64_t)lp.rounds);
-    h->info.algo_bytes = total * 17 + P * ((uint64_t)ep->iters * 108 + sizeof(lcm_epi_result) + sizeof(lcm_lo_info));
-    rc = lcm::epi_download(h, P, total, results, mask); if (rc) return rc;
-    rc = lcm::lo_download(h, P, info); if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return LCM_OK;
-}
 
 int lo_select_impl(lcm_handle* h, const int32_t* counts, int iters, int32_t* seeds_out) {
     if (!h || !seeds_out) return fail(LCM_ERR_INVALID_ARG, "bad argument");
@@ -146,7 +112,10 @@ extern "C" {
 void lcm_lo_params_default(lcm_lo_params* p) { if (p) lcm::lo_params_default(p); }
 int lcm_lo_verify_pairs(lcm_handle* h, const lcm_point_pair* pts, const size_t* offsets, int n_pairs, const lcm_epi_params* ep,
                         const lcm_lo_params* lp, lcm_epi_result* results, lcm_lo_info* info, uint8_t* mask) {
-    return guarded([&] { return lo_verify_pairs_impl(h, pts, offsets, n_pairs, ep, lp, results, info, mask); });
+    return guarded([&] {
+        lcm::VerifyPlan plan{ep, true, false, results, mask, info};
+        return lcm::verify_pairs(h, pts, offsets, n_pairs, &plan, lp);
+    });
 }
 int lcm_lo_select(lcm_handle* h, const int32_t* counts, int iters, int32_t* seeds_out) {
     return guarded([&] { return lo_select_impl(h, counts, iters, seeds_out); });

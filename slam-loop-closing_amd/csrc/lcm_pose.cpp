@@ -1,12 +1,11 @@
 // lcm_pose.cpp — the host side of the relative-pose recovery (include/lcm.h, lcm_pose_*): src/main.cpp:1405-1421 over point
 // lists.  The kernel is lcm_pose.hip's, the arithmetic lcm_pose_device.h's, the pure checks and the choice of the best loop
-// lcm_pose_host.h's.  The store's forms (lcm_pose_db_*) live in lcm_l2.cpp beside the RANSAC whose records they read; they
-// enqueue through pose_enqueue.  Part of liblcm_hip.so's host side; shared state and helpers: lcm_internal.h.
+// lcm_pose_host.h's.  The store's forms (lcm_pose_db_*) live in lcm_l2.cpp beside the RANSAC whose records they read; there the
+// stage runs through lcm_verify.cpp's pipeline.  Part of liblcm_hip.so's host side; shared state and helpers: lcm_internal.h.
 #include "lcm_internal.h"
 
 #include "lcm_epi_device.h"
 #include "lcm_pose_device.h"
-#include "lcm_pose_host.h"
 
 static_assert(sizeof(lcm_pose_result) == 128 && sizeof(lcm::PoseResult) == 128 && sizeof(lcm_pose_params) == 32, "record sizes");
 static_assert(offsetof(lcm_pose_result, t) == 72 && offsetof(lcm::PoseResult, t) == 72 && offsetof(lcm_pose_result, counts) == 96 &&
@@ -31,11 +30,7 @@ static PoseArgs pose_args(lcm_handle* h, const uint4* d_pts, const uint64_t* d_o
 static int pose_launch(lcm_handle* h, const PoseArgs& a, size_t n_pairs, uint32_t* launches) {
     const hipError_t e = launch_pose_recover(a, (uint32_t)n_pairs, h->stream);
     if (e != hipSuccess) return fail(LCM_ERR_HIP, "pose kernel launch failed: %s", hipGetErrorString(e));
-    uint32_t lim = 1;
-    const hipError_t e2 = grid_y_limit(&lim);
-    if (e2 != hipSuccess) return fail(LCM_ERR_HIP, "grid limit: %s", hipGetErrorString(e2));
-    *launches = (uint32_t)((n_pairs + lim - 1) / lim);
-    return LCM_OK;
+    return pair_slices(n_pairs, launches);
 }
 
 int pose_enqueue(lcm_handle* h, const uint4* d_pts, const uint64_t* d_off, size_t n_pairs, size_t total, const double* d_E,
@@ -68,9 +63,7 @@ int pose_recover_pairs_impl(lcm_handle* h, const lcm_point_pair* pts, const size
     int rc = lcm::pose_params_checked(pp_in, &pp); if (rc) return rc;
     size_t total = 0;
     uint32_t max_n = 0;
-    bool capacity = false;
-    if (const char* what = lcm::epi_offsets_problem(offsets, n_pairs, lcm::EPI_MAX_POINTS, &total, &max_n, &capacity))
-        return fail(capacity ? LCM_ERR_CAPACITY : LCM_ERR_INVALID_ARG, "%s", what);
+    rc = lcm::offsets_checked(offsets, n_pairs, &total, &max_n); if (rc) return rc;
     if ((n_pairs > 0 && (!results || !E)) || (total > 0 && !pts)) return fail(LCM_ERR_INVALID_ARG, "NULL buffer");
     if (n_pairs == 0) return LCM_OK;
     rc = set_device(h); if (rc) return rc;
