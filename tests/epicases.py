@@ -62,3 +62,9 @@ def integer_cases():
     E.setflags(write=False)
     pts.setflags(write=False)
     return E, pts
+
+
+def model_set(rng):
+    """130 matrices whose counts spread from none to all: the true E, perturbed more and more, then noise."""
+    scale = np.concatenate([[0.0], np.logspace(-7, 0, 119), np.full(10, 10.0)])
+    return R.E_TRUE[None, :] + scale[:, None] * rng.standard_normal((130, 9))

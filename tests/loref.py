@@ -117,7 +117,8 @@ def refit(cur, a, b, c, d, t, m, route="eigh"):
     if route == "eigh":
         f = np.linalg.eigh(moments(rows))[1][:, 0]
     elif route == "svd":
-        f = np.linalg.svd(rows, full_matrices=True)[2][-1]
+        # with 9 rows or more the economy form holds the same last right singular vector, without the |S| x |S| factor
+        f = np.linalg.svd(rows, full_matrices=len(rows) < 9)[2][-1]
     else:
         f = jacobi_eigvec(moments(rows))
     E = project(T2.T @ f.reshape(3, 3) @ T1)

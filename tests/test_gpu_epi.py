@@ -12,6 +12,7 @@ import pytest
 
 import epicases as S
 import epiref as R
+from verifychecks import check_closure
 
 pytestmark = pytest.mark.gpu
 
@@ -52,12 +53,6 @@ def test_fewer_than_eight_points_have_no_hypotheses(pkg, matcher):
 
 
 # ---- 2. the scoring, exact -----------------------------------------------------------------------------------------------
-def model_set(rng):
-    """130 matrices whose counts spread from none to all: the true E, perturbed more and more, then noise."""
-    scale = np.concatenate([[0.0], np.logspace(-7, 0, 119), np.full(10, 10.0)])
-    return R.E_TRUE[None, :] + scale[:, None] * rng.standard_normal((130, 9))
-
-
 @pytest.mark.parametrize("n", (1, 63, 64, 65, 1025))
 def test_scoring_parity(pkg, matcher, n):
     # the integer-coordinate cases under K = (1, 1, 0, 0), with the all-zero matrix
@@ -70,7 +65,7 @@ def test_scoring_parity(pkg, matcher, n):
     np.testing.assert_array_equal(got, R.counts(models, pts_int[:n], 1.0, S.K_UNIT))
     # 130 matrices over a scene's points, K = (700, 700, 320, 240), at 1 px and at 0.25 px
     pts = S.scene("s1025")[0][:n]
-    models = np.concatenate([model_set(np.random.default_rng(n))[:129], np.zeros((1, 9))])       # 130: the call pads to 192
+    models = np.concatenate([S.model_set(np.random.default_rng(n))[:129], np.zeros((1, 9))])       # 130: the call pads to 192
     for thr in (1.0, 0.25):
         got = matcher.epi_score_models(pts, models, params(pkg, threshold=thr))
         want = R.counts(models, pts, thr)
@@ -88,20 +83,6 @@ def verified(pkg, matcher):
     res, mask = matcher.epi_verify_pairs(pts, offs, ep)
     hyp = [matcher.epi_hypotheses(pts[int(offs[p]):int(offs[p + 1])], p, ep) for p in range(len(scenes))]
     return pts, offs, scenes, res.copy(), mask.copy(), hyp
-
-
-def check_closure(res, mask, pts, offs, hyps, pairs, threshold=1.0):
-    """n_inliers, best_iter, E and every mask byte of the pairs against the numpy closure over the device's hypotheses."""
-    for p in pairs:
-        lo, hi = int(offs[p]), int(offs[p + 1])
-        _, E = hyps[p]
-        n_in, best, m = R.closure(E, pts[lo:hi], threshold)
-        r = res[p]
-        assert (r["n_points"], r["n_inliers"], r["best_iter"]) == (hi - lo, n_in, best), (p, r, n_in, best)
-        assert r["status"] == (1 if hi - lo < 8 else 0)
-        np.testing.assert_array_equal(mask[lo:hi], m, err_msg=str(p))
-        assert int(mask[lo:hi].sum()) == r["n_inliers"]
-        assert as_bytes(r["E"]) == as_bytes(E[best])
 
 
 def test_closure_on_the_devices_own_hypotheses(verified):

@@ -13,6 +13,7 @@ import epicases as ES
 import epiref as E_
 import posecases as S
 import poseref as P
+from verifychecks import check_against_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -25,17 +26,6 @@ def params(pkg, **over):
 
 def as_bytes(a):
     return np.ascontiguousarray(a).tobytes()
-
-
-def check_against_reference(res, mask, pts, offs, E, mask_in, max_depth, k=E_.K):
-    """Every field of every record and every mask byte against poseref."""
-    want, want_mask = P.recover_pairs(E, pts, offs, mask_in, max_depth, k)
-    for p, w in enumerate(want):
-        r = res[p]
-        got = (list(r["counts"]), r["choice"], r["n_good"], r["n_used"], r["status"])
-        assert got == (list(w["counts"]), w["choice"], w["n_good"], w["n_used"], w["status"]), (p, got, w)
-        assert as_bytes(r["R"]) == as_bytes(w["R"]) and as_bytes(r["t"]) == as_bytes(w["t"]), (p, r["R"] - w["R"], r["t"] - w["t"])
-    np.testing.assert_array_equal(mask, want_mask)
 
 
 def check_closure(matcher, res, mask, pts, offs, E, mask_in, max_depth, pairs, k=E_.K):
