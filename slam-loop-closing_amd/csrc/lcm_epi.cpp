@@ -1,6 +1,6 @@
 // lcm_epi.cpp — the host side of the essential-matrix RANSAC (include/lcm.h, lcm_epi_*): src/main.cpp:1395-1403 over point
 // lists.  The kernels are lcm_epi.hip's, the arithmetic lcm_epi_device.h's, the pure checks lcm_epi_host.h's.  The stage runs
-// through lcm_verify.cpp's pipeline: lcm_epi_verify_pairs here, the store's forms (lcm_epi_db_*) in lcm_l2.cpp beside the list
+// through lcm_verify.cpp's pipeline: lcm_epi_verify_pairs here, the store's forms (lcm_epi_db_*) in lcm_l2_db.cpp beside the list
 // kernels whose records they read.
 // Part of liblcm_hip.so's host side; shared state and helpers: lcm_internal.h.
 #include "lcm_internal.h"

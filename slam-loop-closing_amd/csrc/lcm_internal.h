@@ -5,8 +5,9 @@
 //   lcm_mfma_host.cpp  opt-in matrix-core variants    lcm_group.cpp    multi-GPU group (RCCL)
 //   lcm_knn.cpp        pair mode with k = 2 neighbours + Lowe's ratio test
 //   lcm_ratio.cpp      bulk / online loop search scored with Lowe's ratio test
-//   lcm_l2.cpp         pair mode on 128-byte SIFT rows under L2 (knnMatch(k = 2) + ratio test), ratio-test counts per pair,
-//                      the SIFT keyframe store (lcm_l2_db_*)
+//   lcm_l2.cpp         pair mode on 128-byte SIFT rows under L2 (knnMatch(k = 2) + ratio test) and ratio-test counts per pair on
+//                      host matrices; the staging and the runs behind both (planned in lcm_l2_host.h)
+//   lcm_l2_db.cpp      the SIFT keyframe store (lcm_l2_db_*): arenas, searches, device-side lists, the loop verification's entry points
 //   lcm_epi.cpp        essential-matrix RANSAC over the loop candidates' correspondences (lcm_epi_*)
 //   lcm_pose.cpp       relative pose of the verified candidates and the best loop (lcm_pose_*)
 //   lcm_lo.cpp         local optimisation of the RANSAC's best hypotheses (lcm_lo_*)
@@ -28,6 +29,7 @@
 #include <vector>
 
 #include "lcm_kernels.h"
+#include "lcm_l2_host.h"
 #include "lcm_verify_host.h"
 
 namespace lcm {
@@ -229,7 +231,7 @@ struct lcm_handle {
     Plan ratio_plan;
     uint8_t* d_ratio_q = nullptr; size_t d_ratio_q_bytes = 0;          // the online call's query rows
     lcm_score* d_ratio_scores = nullptr; size_t d_ratio_scores_n = 0;  // ... and its records
-    // pair mode on SIFT rows (lcm_l2.cpp): raw rows, operand image and per-row words of the call's matrices in the tile
+    // pair mode on SIFT rows (lcm_l2.cpp, lcm_l2_db.cpp): raw rows, operand image and per-row words of the call's matrices in the tile
     // space, the tables, per-item keys, folded results (device + pinned landing zone), the rescan's flag list
     struct L2Scratch {
         uint8_t* d_raw = nullptr;  size_t d_raw_n = 0;
@@ -252,7 +254,7 @@ struct lcm_handle {
         uint4* d_rec = nullptr;    size_t d_rec_n = 0;
         uint4* d_rec_pts = nullptr; size_t d_rec_pts_n = 0;
     } l2;
-    // the SIFT keyframe store (lcm_l2_db_*, lcm_l2.cpp): three arenas in ONE tile space (lcm_kernels.h) with room for
+    // the SIFT keyframe store (lcm_l2_db_*, lcm_l2_db.cpp): three arenas in ONE tile space (lcm_kernels.h) with room for
     // cap_tiles tiles, slot f's frame at tile tile0[f] (tile0 has size + 1 entries: the last is the first free tile), the
     // device frame table {first tile, rows} per slot, and the tables of the last search.  A fourth arena in the same tile
     // space, d_pts (8 bytes per row: a keypoint's x, y as bits), exists from the first frame that arrives with points
@@ -419,6 +421,49 @@ int stored_src(lcm_handle* h, int frame_id, RowSrc* out, int* n_kp);    // devic
 // frames train_ids; else the stored pairs): job_of[p] = pair p's job, -1 when a side is empty.
 int batch_jobs(lcm_handle* h, const uint8_t* q_host, int nq_host, const lcm_pair_ref* pairs, const int32_t* train_ids,
                int n_pairs, std::vector<PairJob>& jobs, std::vector<int>& job_of, size_t* stage_bytes);
+// ---- lcm_l2.cpp: the SIFT matcher's checks, staging and runs, shared with lcm_l2_db.cpp (the plans: lcm_l2_host.h)
+int l2_check_knn(const lcm_handle* h, double ratio);    // what every k = 2 call refuses (lcm_knn.cpp's rule)
+int l2_check_rows(int n);                               // a SIFT matrix holds 0 .. 65535 rows
+int l2_refused(const char* what);                       // a planner's answer: LCM_OK for NULL, else LCM_ERR_CAPACITY and the message
+// Where a call's matrices are: raw rows, operand image and row words in one tile space, matrix f at tile tile0[f].  The store's
+// slots (lcm_l2_db.cpp) are there already, packed when they were appended.  A host call's matrices (lcm_l2.cpp, call_where) go
+// into the handle's scratch: tile_meta / n_tiles are the tiles to pack, frames / rows / n_frames the matrices to upload first
+// (rows[f] == 0: none).  Every pointer is the caller's.
+struct L2Where {
+    const uint8_t* d_raw; const uint8_t* d_img; const uint32_t* d_tw; const uint32_t* tile0;
+    const uint32_t* tile_meta = nullptr; size_t n_tiles = 0;
+    const uint8_t* const* frames = nullptr; const int* rows = nullptr; int n_frames = 0;
+};
+// A list run: its plan; once enqueued, the job table on the device and the host table block, which is pageable and has to stay
+// alive until the stream has been waited for
+struct L2Run { L2RunPlan plan; const L2Job* d_jobs = nullptr; std::vector<uint8_t> tab; };
+int l2_enqueue(lcm_handle* h, const L2Where& w, L2Run& run);                  // final_keys -> h->l2.d_fin, nothing waited for
+int l2_count_run(lcm_handle* h, const L2Where& w, const L2CountPlan& pl, size_t n_pairs, double ratio, const lcm_l2_score** rec);
+// lcm_match_pairs_ratio_l2 / lcm_score_pairs_ratio_l2; stored != NULL: over the store's slots (frames unused, rows / n_frames the store's)
+int l2_match_pairs(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_frames, const lcm_pair_ref* pairs, int n_pairs,
+                   double ratio, lcm_dmatch* out, size_t cap, size_t* offsets, const L2Where* stored);
+int l2_score_pairs(lcm_handle* h, const uint8_t* const* frames, const int* rows, int n_frames, const lcm_pair_ref* pairs, int n_pairs,
+                   double ratio, lcm_l2_score* scores, const L2Where* stored);
+int l2_candidates_out(const L2StorePlan& pl, const int* rows, size_t S, const std::vector<L2StoreCurr>& currs, const lcm_l2_score* rec,
+                      int min_matches, lcm_loop_candidate* out, size_t cap, size_t* n_out, size_t* n_pairs_out);
+// A caller's pair table over n_frames matrices -> live[job_of[p]] = pair p, job_of[p] = -1 when a side is empty.  Pair p's
+// positions are range-checked, then extra(q, t) may refuse it (a status), before pair p + 1 is looked at.
+struct L2NoCheck { int operator()(int, int) const { return LCM_OK; } };
+template <typename Extra = L2NoCheck>
+int l2_read_pairs(const lcm_pair_ref* pairs, size_t n_pairs, const int* rows, int n_frames, std::vector<L2Pair>& live,
+                  std::vector<int>& job_of, Extra&& extra = Extra{}) {
+    live.clear();
+    job_of.assign(n_pairs, -1);
+    for (size_t p = 0; p < n_pairs; ++p) {
+        const int q = pairs[p].query_frame_id, t = pairs[p].train_frame_id;
+        if (q < 0 || q >= n_frames || t < 0 || t >= n_frames) return fail(LCM_ERR_INVALID_ARG, "pair %d: position outside [0, %d)", (int)p, n_frames);
+        if (const int rc = extra(q, t)) return rc;
+        if (rows[q] == 0 || rows[t] == 0) continue;
+        job_of[p] = (int)live.size();
+        live.push_back(L2Pair{q, t});
+    }
+    return LCM_OK;
+}
 // ---- lcm_epi.cpp, lcm_lo.cpp, lcm_pose.cpp: the stages of the loop verification.  Every *_enqueue works on h's stream over
 // n_pairs pairs whose records d_pts[d_off[p] .. d_off[p + 1]) are on the device (max_n = the longest pair, total =
 // d_off[n_pairs]), sets *launches to the kernel launches it made and does not wait; every *_download enqueues the copies of
@@ -444,7 +489,7 @@ int lo_download(lcm_handle* h, size_t n_pairs, lcm_lo_info* info);
 int pose_enqueue(lcm_handle* h, const uint4* d_pts, const uint64_t* d_off, size_t n_pairs, size_t total, const double* d_E,
                  uint32_t e_stride, const uint8_t* d_mask_in, const lcm_epi_params& ep, const lcm_pose_params& pp, uint32_t* launches);
 int pose_download(lcm_handle* h, size_t n_pairs, size_t total, lcm_pose_result* results, uint8_t* mask);
-// ---- lcm_verify.cpp: the stages as one pipeline over a VerifyPlan (lcm_verify_host.h); lcm_l2.cpp runs it on the list kernel's
+// ---- lcm_verify.cpp: the stages as one pipeline over a VerifyPlan (lcm_verify_host.h); lcm_l2_db.cpp runs it on the list kernel's
 // point records
 // *slices = launches of a kernel whose grid's y is the pair: ceil(n_pairs / grid_y_limit())
 int pair_slices(size_t n_pairs, uint32_t* slices);
@@ -464,6 +509,9 @@ int verify_pairs(lcm_handle* h, const lcm_point_pair* pts, const size_t* offsets
 namespace {
 using lcm::cross_score_prefixes;
 using lcm::eligible_prefix;
+using lcm::L2Pair;
+using lcm::L2Run;
+using lcm::L2Where;
 using lcm::launch_and_time;
 using lcm::PairJob;
 using lcm::RowSrc;

@@ -1,7 +1,7 @@
 // lcm_lo.cpp — the host side of the RANSAC's local optimisation (include/lcm.h, lcm_lo_*): the refit of the 64 best
 // hypotheses on their inliers, between the RANSAC (lcm_epi.cpp) and the pose recovery (lcm_pose.cpp).  The kernels are
 // lcm_lo.hip's, the arithmetic lcm_lo_device.h's, the pure checks lcm_lo_host.h's.  The stage runs through lcm_verify.cpp's
-// pipeline: lcm_lo_verify_pairs here, the store's forms (lcm_lo_db_*) in lcm_l2.cpp.  Part of liblcm_hip.so's host side;
+// pipeline: lcm_lo_verify_pairs here, the store's forms (lcm_lo_db_*) in lcm_l2_db.cpp.  Part of liblcm_hip.so's host side;
 // shared state and helpers: lcm_internal.h.
 #include "lcm_internal.h"
 

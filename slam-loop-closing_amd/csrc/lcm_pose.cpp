@@ -1,6 +1,6 @@
 // lcm_pose.cpp — the host side of the relative-pose recovery (include/lcm.h, lcm_pose_*): src/main.cpp:1405-1421 over point
 // lists.  The kernel is lcm_pose.hip's, the arithmetic lcm_pose_device.h's, the pure checks and the choice of the best loop
-// lcm_pose_host.h's.  The store's forms (lcm_pose_db_*) live in lcm_l2.cpp beside the RANSAC whose records they read; there the
+// lcm_pose_host.h's.  The store's forms (lcm_pose_db_*) live in lcm_l2_db.cpp beside the RANSAC whose records they read; there the
 // stage runs through lcm_verify.cpp's pipeline.  Part of liblcm_hip.so's host side; shared state and helpers: lcm_internal.h.
 #include "lcm_internal.h"
 

@@ -1,6 +1,6 @@
 // lcm_verify.cpp — the loop verification as one staged pipeline over a lcm::VerifyPlan (lcm_verify_host.h): the RANSAC
 // (lcm_epi.cpp), the local optimisation (lcm_lo.cpp) and the pose recovery (lcm_pose.cpp), each enqueued behind the one
-// before on the same point records.  The store's list calls (lcm_l2.cpp, store_lists) and the host-list calls
+// before on the same point records.  The store's list calls (lcm_l2_db.cpp, store_lists) and the host-list calls
 // lcm_epi_verify_pairs / lcm_lo_verify_pairs run their plan through verify_enqueue and verify_download; a new stage is a flag
 // of the plan and its lines in verify_empty, verify_enqueue and verify_download.  Part of liblcm_hip.so's host side; shared
 // state and helpers: lcm_internal.h.

@@ -1,4 +1,4 @@
-"""The essential-matrix RANSAC on the device (include/lcm.h lcm_epi_*; lcm_epi.hip, lcm_epi.cpp, lcm_l2.cpp) against
+"""The essential-matrix RANSAC on the device (include/lcm.h lcm_epi_*; lcm_epi.hip, lcm_epi.cpp, lcm_l2_db.cpp) against
 tests/epiref.py.  Needs a real MI355X.
 
 The sampler and the scoring are compared exactly: integers there, and the header's arithmetic (double, every product and sum

@@ -1,5 +1,5 @@
 """The store's loop correspondences made on the device (lcm_l2_db_append_kp, lcm_l2_db_read_kp, lcm_l2_db_match_points,
-lcm_l2_db_detect_loops_points: lcm_l2.cpp, lcm_l2_emit.hip) against tests/l2ref.py (knn2 + ratio_filter) plus a numpy gather
+lcm_l2_db_detect_loops_points: lcm_l2_db.cpp, lcm_l2_emit.hip) against tests/l2ref.py (knn2 + ratio_filter) plus a numpy gather
 of the keypoints and, as a second witness, against lcm_l2_db_match_pairs_ratio on the same store, whose `out` and `offsets`
 they must equal byte for byte.  Needs a real MI355X.
 

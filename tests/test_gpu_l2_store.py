@@ -1,4 +1,4 @@
-"""The SIFT keyframe store (lcm_l2_db_*: lcm_l2.cpp, lcm_l2_store.hip) against tests/l2ref.py through tests/l2countcases.py
+"""The SIFT keyframe store (lcm_l2_db_*: lcm_l2_db.cpp, lcm_l2_store.hip) against tests/l2ref.py through tests/l2countcases.py
 and, as a second witness, against the host-matrix calls on the same frames (lcm_score_pairs_ratio_l2,
 lcm_match_pairs_ratio_l2, lcm_loop_search_ratio_l2).  Needs a real MI355X.
 

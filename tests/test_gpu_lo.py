@@ -1,4 +1,4 @@
-"""The RANSAC's local optimisation on the device (include/lcm.h lcm_lo_*; lcm_lo.hip, lcm_lo.cpp, lcm_l2.cpp) against
+"""The RANSAC's local optimisation on the device (include/lcm.h lcm_lo_*; lcm_lo.hip, lcm_lo.cpp, lcm_l2_db.cpp) against
 tests/loref.py.  Needs a real MI355X.
 
 The selection is integers and compared exactly.  One refit round is compared through the seam: the selected set and the status

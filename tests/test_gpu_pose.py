@@ -1,4 +1,4 @@
-"""The relative-pose recovery on the device (include/lcm.h lcm_pose_*; lcm_pose.hip, lcm_pose.cpp, lcm_l2.cpp) against
+"""The relative-pose recovery on the device (include/lcm.h lcm_pose_*; lcm_pose.hip, lcm_pose.cpp, lcm_l2_db.cpp) against
 tests/poseref.py.  Needs a real MI355X.
 
 Everything is compared exactly: the model is +, -, x, / and square roots in double with every product and sum rounded on its
