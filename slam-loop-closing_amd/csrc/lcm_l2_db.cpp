@@ -294,13 +294,8 @@ int store_lists(lcm_handle* h, const int* rows, const std::vector<L2Pair>& live,
     const size_t P = live.size(), total_rows = rp.row0[P];
 
     // [first block of the first live pair at or after p, p <= n_pairs | survivors per block, + their total]
-    std::vector<uint32_t> pair_block(n_pairs + 1);
-    uint32_t next = (uint32_t)rp.n_blocks;
-    pair_block[n_pairs] = next;
-    for (size_t p = n_pairs; p-- > 0;) {
-        if (job_of[p] >= 0) next = rp.jobs[(size_t)job_of[p]].reserved;
-        pair_block[p] = next;
-    }
+    std::vector<uint32_t> pair_block;
+    lcm::l2_pair_block(job_of, rp.jobs, rp.n_blocks, pair_block);
     auto& s = h->l2;
     rc = ensure_dev(s.d_blocks, s.d_blocks_n, n_pairs + 1 + rp.n_blocks + 1); if (rc) return rc;
     rc = ensure_dev(s.d_offsets, s.d_offsets_n, n_pairs + 1); if (rc) return rc;

@@ -70,6 +70,19 @@ inline const char* l2_run_plan(const std::vector<L2Pair>& pairs, const int* rows
     return nullptr;
 }
 
+// k_l2_emit_offsets' table over the pairs of a list CALL (job_of[p] = pair p's job, -1 when a side is empty): the first block
+// of the first live pair at or after p, for every p <= n_pairs; n_blocks past the last live pair
+inline void l2_pair_block(const std::vector<int>& job_of, const std::vector<L2Job>& jobs, size_t n_blocks, std::vector<uint32_t>& pair_block) {
+    const size_t n_pairs = job_of.size();
+    pair_block.resize(n_pairs + 1);
+    uint32_t next = (uint32_t)n_blocks;
+    pair_block[n_pairs] = next;
+    for (size_t p = n_pairs; p-- > 0;) {
+        if (job_of[p] >= 0) next = jobs[(size_t)job_of[p]].reserved;
+        pair_block[p] = next;
+    }
+}
+
 // A count run over the live pairs: one item per query chunk of a pair, whatever the train matrix's size; live[j]'s record is j
 struct L2CountPlan { std::vector<L2CountItem> items; int chunk_rows = 0; uint64_t distances = 0; };
 inline const char* l2_count_plan(const std::vector<L2Pair>& live, const int* rows, const uint32_t* tile0, L2CountPlan& pl) {

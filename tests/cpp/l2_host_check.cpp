@@ -155,6 +155,50 @@ static const Dump STORE_MIN0_ALL = {
 static const Dump STORE_EMPTY = {
     128, 0, 0, 0, 0, 0, 0, 9999, 9999, 0, 0, 9999, 9999, 9999, 9999, 9999, 9999,};
 
+// A list CALL over `rows` whose pairs may have an empty side (lcm_l2_db_match_points: live = the pairs with rows on both sides,
+// job_of[p] = pair p's job or -1): l2_run_plan's block and row prefixes and l2_pair_block against sums taken pair by pair from
+// the row counts alone.  Returns the call's blocks.
+static size_t check_ragged_call(const std::vector<int>& rows, const std::vector<L2Pair>& call) {
+    std::vector<uint32_t> tile0, tile_meta;
+    lcm::l2_tile_space(rows.data(), (int)rows.size(), tile0, tile_meta);
+    std::vector<L2Pair> live;
+    std::vector<int> job_of;
+    for (const L2Pair& p : call) {
+        const bool has = rows[(size_t)p.q] > 0 && rows[(size_t)p.t] > 0;
+        job_of.push_back(has ? (int)live.size() : -1);
+        if (has) live.push_back(p);
+    }
+    lcm::L2RunPlan pl;
+    CHECK(lcm::l2_run_plan(live, rows.data(), tile0.data(), pl) == nullptr);
+    CHECK(pl.jobs.size() == live.size() && pl.row0.size() == live.size() + 1);
+    // block_at[p] / row_at[p]: blocks and query rows of the live pairs BEFORE position p of the call
+    std::vector<uint64_t> block_at(call.size() + 1, 0), row_at(call.size() + 1, 0);
+    int longest = 0;
+    for (size_t p = 0; p < call.size(); ++p) {
+        const int nq = job_of[p] >= 0 ? rows[(size_t)call[p].q] : 0;
+        block_at[p + 1] = block_at[p] + (uint64_t)((nq + 255) / 256);
+        row_at[p + 1] = row_at[p] + (uint64_t)nq;
+        longest = std::max(longest, nq);
+    }
+    CHECK(pl.n_blocks == block_at[call.size()] && pl.row0[live.size()] == row_at[call.size()] && pl.max_nq == longest);
+    for (size_t p = 0; p < call.size(); ++p) {
+        if (job_of[p] < 0) continue;
+        const lcm::L2Job& j = pl.jobs[(size_t)job_of[p]];
+        CHECK(j.reserved == block_at[p] && j.out_row0 == row_at[p] && pl.row0[(size_t)job_of[p]] == row_at[p]);
+        CHECK(j.nq == (uint32_t)rows[(size_t)call[p].q] && j.nt == (uint32_t)rows[(size_t)call[p].t]);
+        CHECK(j.q_tile == tile0[(size_t)call[p].q] && j.t_tile == tile0[(size_t)call[p].t]);
+    }
+    std::vector<uint32_t> pair_block(3, 77u);                      // resized and overwritten whole
+    lcm::l2_pair_block(job_of, pl.jobs, pl.n_blocks, pair_block);
+    CHECK(pair_block.size() == call.size() + 1);
+    for (size_t p = 0; p <= call.size() && p < pair_block.size(); ++p) {
+        size_t k = p;
+        while (k < call.size() && job_of[k] < 0) ++k;              // the first live pair at or after p; none: every block lies before
+        CHECK(pair_block[p] == block_at[k]);
+    }
+    return pl.n_blocks;
+}
+
 static void pin(const char* v) {
     if (v) { setenv("LCM_TUNE_L2_CHUNK", v, 1); setenv("LCM_TUNE_L2_COUNT_CHUNK", v, 1); }
     else { unsetenv("LCM_TUNE_L2_CHUNK"); unsetenv("LCM_TUNE_L2_COUNT_CHUNK"); }
@@ -207,6 +251,24 @@ int main() {
             const lcm::L2CountItem& i = cp.items[p];
             CHECK(i.q_tile == 0 && i.q_rows == 1 && i.t_tile == 1 && i.t_rows == 1 && i.pair == p && i.reserved[0] == 0 && i.reserved[1] == 0 && i.reserved[2] == 0);
         }
+    }
+
+    // Ragged tall calls (the store's list route, lcm_l2_db.cpp's store_lists): frames of 65535, 0, 1, 257, 32768 and 65535 rows;
+    // live and empty-sided pairs interleaved, empty pairs first and last, every pair empty, no pair at all; both chunk pins
+    {
+        const std::vector<int> tall = {65535, 0, 1, 257, 32768, 65535};
+        const std::vector<L2Pair> interleaved = {{0, 5}, {2, 0}, {1, 0}, {4, 5}, {3, 0}, {0, 1}, {5, 5}, {1, 1}, {2, 3}, {5, 0}};
+        const std::vector<L2Pair> ends = {{1, 0}, {0, 1}, {5, 0}, {3, 4}, {1, 1}, {1, 5}, {0, 0}, {4, 2}, {2, 1}, {1, 3}};
+        const std::vector<L2Pair> none = {{1, 0}, {0, 1}, {1, 1}, {5, 1}};
+        for (const char* v : {(const char*)nullptr, "128", "256"}) {
+            pin(v);
+            CHECK(check_ragged_call(tall, interleaved) == 256 + 1 + 128 + 2 + 256 + 1 + 256);
+            CHECK(check_ragged_call(tall, ends) == 256 + 2 + 256 + 128);
+            CHECK(check_ragged_call(tall, none) == 0);
+            CHECK(check_ragged_call(tall, {}) == 0);
+            CHECK(check_ragged_call(tall, std::vector<L2Pair>(300, L2Pair{5, 2})) == 300 * 256);      // 76800 blocks, 19 660 500 rows
+        }
+        pin(nullptr);
     }
 
     // The store: slot 0 is skipped, slot 1 is empty (below min_rows = 100; admitted and empty with min_rows = 0), slot 2 holds

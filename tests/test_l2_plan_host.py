@@ -14,7 +14,10 @@ def test_planners_run_clean_under_sanitizers(tmp_path):
     either side, one matrix as both sides, an empty matrix, a matrix that no pair names (tiles in the list plan, none in the
     count plan), 1023 and 1024 items-at-256 with the pin unset / 128 / 256 / illegal, and a store with a skipped slot, slots
     below and at min_rows, an empty admitted slot, last_past of -1, 0 and beyond the last slot, a curr without a run and several
-    currs in one search.  Built as plain C++ (HIP's headers for lcm_kernels.h's types only, no runtime is linked) with ASan +
+    currs in one search.  Ragged tall calls (frames of 65535, 0, 1, 257, 32768 and 65535 rows; live and empty-sided pairs
+    interleaved, empty pairs first and last, all empty, none, 300 pairs of 256 blocks; both chunk pins): every job's `reserved`
+    and `out_row0`, `n_blocks`, `max_nq` and l2_pair_block for every p <= n_pairs against sums taken from the row counts alone.
+    Built as plain C++ (HIP's headers for lcm_kernels.h's types only, no runtime is linked) with ASan +
     UBSan (no recovery) and run on the CPU: exit status 0 and no report."""
     exe = tmp_path / "l2_host_check"
     subprocess.check_call([CLANG, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
