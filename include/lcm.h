@@ -653,6 +653,105 @@ LCM_API int  lcm_pose_db_detect_loops(lcm_handle* h, int curr, const uint8_t* qu
                                       lcm_pose_result* pose_results, lcm_dmatch* out, lcm_point_pair* pts, uint8_t* mask,
                                       uint8_t* pose_mask, size_t cap, size_t* offsets, int floor_inliers, int* best);
 
+/* ---- closing the loop: pose-graph Gauss-Newton correction on the device --------------------------------------------------- */
+/* src/main.cpp:1429-1491: the pose graph of :1441-1470, optimizePoseGraph (:282-445) and the drift of :1476-1480.  The
+ * reference takes a central-difference Jacobian over all 6 (N - 1) parameters, re-evaluates every edge per column and solves a
+ * dense system; a column is exactly zero outside the two poses of an edge, so the twelve columns per edge computed here ARE
+ * its Jacobian, and the solve is an exact block Cholesky of the same matrix (lcm_pgo_device.h, lcm_pgo.hip).
+ * In double, every product and sum rounded on its own, sums left to right:
+ *   conventions  a pose is world-to-camera, Xc = R Xw + t (R row-major); an edge says R_to = R_rel R_from,
+ *                t_to = R_rel t_from + t_rel (:78-86)
+ *   parameters   pose 0 is fixed; pose i >= 1 has p_i = (log R_i, t_i), the rotation vector and the translation
+ *   exp(r)       theta = sqrt(r . r); theta < DBL_EPSILON: I; else k = r / theta and
+ *                R = cos(theta) I + (1 - cos(theta)) k k^T + sin(theta) [k]x
+ *   log(R)       v = (R21 - R12, R02 - R20, R10 - R01) / 2, s = sqrt(v . v), c = (trace - 1) / 2 clamped to [-1, 1];
+ *                s >= 1e-5: v atan2(s, c) / s;  s < 1e-5 and c > 0: v itself;  s < 1e-5 and c <= 0: the run ends with
+ *                LCM_PGO_HALF_TURN.  R is taken as a rotation and is not projected.  This is NOT cv::Rodrigues bit for bit:
+ *                OpenCV returns an exact zero vector below s = 1e-5, which, as the sequential edges are built from the poses
+ *                themselves and eps = 1e-6, makes every sequential edge's rotational Jacobian exactly zero in iteration 0.
+ *                The first-order branch removes that artefact and changes nothing for s >= 1e-5.
+ *   residual     of edge e (:358-381), w = sqrt(weight): r[0..3) = w log((R_rel R_from)^T R_to),
+ *                r[3..6) = w (t_to - (R_rel t_from + t_rel))
+ *   Jacobian     per edge twelve columns, the six parameters of `from`, then of `to`; a column is
+ *                (r(p + eps e_c) - r(p - eps e_c)) / (2 eps).  The columns of pose 0 are not parameters (zero in `jac`).
+ *   normal eq.   H = sum_e J_e^T J_e, g = sum_e J_e^T r_e, each 6 x 6 block and 6-vector one running sum over its edges in
+ *                ascending edge order, within an edge over the residual's rows; lambda = damping trace(H) / (6 (n_poses - 1)):
+ *                the divisor counts every pose but pose 0, valid or not, as the reference's numParams does; H += lambda I;
+ *                H dp = -g by Cholesky.  A pivot that is not > 0 (NaN included) ends the run BEFORE the update with
+ *                LCM_PGO_SOLVE_FAILED (the reference's !ok branch).
+ *   update       p += dp, max_update = max |dp_k|, cost = r . r of the iteration's residuals before the update (:426-440);
+ *                max_update < min_update ends the run as LCM_PGO_CONVERGED after that iteration, max_iters iterations
+ *                without it as LCM_PGO_MAX_ITERS
+ *   write-back   pose 0 byte for byte; every other valid pose as exp of its rotation parameters and its t (:316-324).  An
+ *                invalid pose is returned byte for byte: the reference turns an empty pose into the identity, this library
+ *                keeps validity as a byte per pose (valid[i] != 0) and leaves such a pose alone; its contents are not read.
+ *                LCM_PGO_HALF_TURN before any update: every pose byte for byte.
+ * Limits: n_poses <= LCM_PGO_MAX_POSES.  An edge with |from - to| == 1 is a chain edge, any other a loop edge, at most
+ * LCM_PGO_MAX_LOOPS of them; the border is the set of poses >= 1 that end a loop edge (at most 16).  With the unknowns ordered
+ * interior poses first, border poses last, H is block-tridiagonal with a border of at most 96 columns, and device memory grows
+ * as O(n_poses x border).  Duplicate edges add.  A valid pose no edge reaches gets dp = 0. */
+#define LCM_PGO_MAX_POSES 4096
+#define LCM_PGO_MAX_LOOPS 8
+typedef struct lcm_pgo_pose { double R[9]; double t[3]; } lcm_pgo_pose;                       /* 96 bytes, R row-major */
+typedef struct lcm_pgo_edge { double R[9]; double t[3]; double weight; int32_t from, to; } lcm_pgo_edge;   /* 112 bytes */
+typedef enum lcm_pgo_loop_direction { LCM_PGO_LOOP_AS_WRITTEN = 0, LCM_PGO_LOOP_INVERTED = 1 } lcm_pgo_loop_direction;
+typedef struct lcm_pgo_params {  /* defaults = the reference's constants */
+    double eps;                  /* 1e-6: the central difference's step, finite and > 0 */
+    double damping;              /* 1e-4: finite and >= 0 */
+    double min_update;           /* 1e-6: finite and >= 0; 0 never converges (every iteration runs) */
+    double loop_weight;          /* 10.0: the loop edge's weight in lcm_pgo_build_graph / lcm_pgo_close_loop, finite and >= 0 */
+    int32_t max_iters;           /* 20, in [1, 100] */
+    int32_t loop_direction;      /* lcm_pgo_loop_direction: lcm_pgo_close_loop only, see there */
+    int32_t reserved[6];         /* ignored */
+} lcm_pgo_params;                /* 64 bytes */
+typedef enum lcm_pgo_status { LCM_PGO_CONVERGED = 0, LCM_PGO_MAX_ITERS = 1, LCM_PGO_SOLVE_FAILED = 2, LCM_PGO_HALF_TURN = 3 } lcm_pgo_status;
+typedef struct lcm_pgo_info {
+    double cost_first, cost_last;     /* r . r of the first and of the last linearisation made (a failed solve's included) */
+    double max_update, lambda;        /* max |dp_k| of the last update applied; the damping of the last linearisation made */
+    int32_t iterations;               /* updates applied */
+    int32_t status;                   /* lcm_pgo_status */
+    int32_t n_params;                 /* 6 x (valid poses other than pose 0): the unknowns solved for */
+    int32_t n_border;                 /* border poses */
+} lcm_pgo_info;                       /* 48 bytes */
+LCM_API void lcm_pgo_params_default(lcm_pgo_params* p);
+/* The whole of optimizePoseGraph.  valid: one byte per pose, NULL = all valid; pp NULL = the defaults; poses_out (n_poses
+ * records) may alias poses.  Refused with LCM_ERR_INVALID_ARG before anything is launched or written: a NULL buffer,
+ * n_poses < 2, n_edges < 1, pose 0 invalid, an edge with from == to, an index out of range or an invalid endpoint, a weight
+ * that is negative or not finite, a non-finite double in a valid pose or an edge, a pose or edge R with max |R R^T - I| > 1e-6
+ * or a negative determinant, a bad pp field; LCM_ERR_CAPACITY above the limits.  Ordered on the handle's stream and finished on
+ * return; lcm_last_launch_info: kernel_ms, launches, pairs = n_edges.  The same call gives the same bytes: no sum's order
+ * depends on scheduling. */
+LCM_API int  lcm_pgo_optimize(lcm_handle* h, const lcm_pgo_pose* poses, const uint8_t* valid, int n_poses, const lcm_pgo_edge* edges,
+                              int n_edges, const lcm_pgo_params* pp, lcm_pgo_pose* poses_out, lcm_pgo_info* info);
+/* The test seam: exactly one iteration from the given poses through the kernels lcm_pgo_optimize launches (pp is checked whole;
+ * max_iters is not used).  params_out: 6 n_poses doubles, the parameters before the update (pose 0's slot: its log where that exists, else
+ * v, and its t; an invalid pose's: zeros); residuals: 6 n_edges; jac: n_edges x 6 x 12 row-major; dp: 6 (n_poses - 1), zero
+ * for invalid poses.  info as lcm_pgo_optimize's with max_iters = 1. */
+LCM_API int  lcm_pgo_step(lcm_handle* h, const lcm_pgo_pose* poses, const uint8_t* valid, int n_poses, const lcm_pgo_edge* edges,
+                          int n_edges, const lcm_pgo_params* pp, double* params_out, double* residuals, double* jac, double* dp,
+                          lcm_pgo_info* info);
+/* Host only (:1441-1470): one edge of weight 1 per pair of poses i - 1, i that are both valid, from the poses
+ * (R_rel = R_i R_{i-1}^T, t_rel = t_i - R_rel t_{i-1}), then the loop edge from = past, to = curr with (R_loop, t_loop) and
+ * pp->loop_weight.  *n_edges = the edges the graph has; more than cap: LCM_ERR_CAPACITY and nothing written to edges_out. */
+LCM_API int  lcm_pgo_build_graph(const lcm_pgo_pose* poses, const uint8_t* valid, int n_poses, int past, int curr, const double* R_loop,
+                                 const double* t_loop, const lcm_pgo_params* pp, lcm_pgo_edge* edges_out, int cap, int* n_edges);
+/* Host only (:1476-1480): *angle = |log(R_loop (R_curr R_past^T)^T)| in radians, with the log above (at half a turn:
+ * atan2(s, c)).  It serves the "before" and the "after" print. */
+LCM_API int  lcm_pgo_rotation_drift(const lcm_pgo_pose* poses, int n_poses, int past, int curr, const double* R_loop, double* angle);
+/* Host only: simplePoseCorrection (:451-492), the reference's other PoseGraphMethod.  With rvec = log(R_loop (R_curr R_past^T)^T),
+ * every valid pose f in (past, curr] gets R_f <- exp(rvec (f - past) / (curr - past)) R_f; everything else is copied.  past < curr;
+ * half a turn of error is refused (LCM_ERR_INVALID_ARG).  poses_out may alias poses. */
+LCM_API int  lcm_pgo_linear_correct(const lcm_pgo_pose* poses, const uint8_t* valid, int n_poses, int past, int curr,
+                                    const double* R_loop, lcm_pgo_pose* poses_out);
+/* lcm_pgo_build_graph on pr's R and t followed by lcm_pgo_optimize; a pr whose status is not LCM_POSE_OK is refused.
+ * pp->loop_direction says how pr becomes the edge.  lcm_pose_* returns X_past = R X_curr + t (query = curr, the argument order of
+ * :1407, what cv::recoverPose(E, ptsCurr, ptsPast, ...) returns), and :1464-1467 puts that pair UNCHANGED on an edge whose own
+ * definition is past -> curr.  LCM_PGO_LOOP_AS_WRITTEN (0, the default) reproduces the reference's lines: R_rel = R, t_rel = t.
+ * LCM_PGO_LOOP_INVERTED (1) uses (R^T, -R^T t), the geometrically consistent reading.  The unit t against the trajectory's scale
+ * stays the caller's concern, as in the reference. */
+LCM_API int  lcm_pgo_close_loop(lcm_handle* h, const lcm_pgo_pose* poses, const uint8_t* valid, int n_poses, int past, int curr,
+                                const lcm_pose_result* pr, const lcm_pgo_params* pp, lcm_pgo_pose* poses_out, lcm_pgo_info* info);
+
 /* ---- loop search against the stored database --------------------------------------------------------- */
 /* Score `query` (id query_frame_id) against every stored frame with query_frame_id - id >= min_gap, ascending
  * slot order.  out_scores / out_frame_ids need room for lcm_db_size() records. */

@@ -91,6 +91,23 @@ class PoseResult(C.Structure):
 POSE_OK, POSE_NO_MODEL = 0, 1            # lcm_pose_status
 
 
+class PgoParams(C.Structure):
+    """lcm_pgo_params: the Gauss-Newton correction's step, damping, stopping rule, the loop edge's weight and direction (64 bytes)."""
+    _fields_ = [("eps", C.c_double), ("damping", C.c_double), ("min_update", C.c_double), ("loop_weight", C.c_double),
+                ("max_iters", C.c_int32), ("loop_direction", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+class PgoInfo(C.Structure):
+    """lcm_pgo_info: the first and last cost, the last update and damping, the iterations, the status, the sizes (48 bytes)."""
+    _fields_ = [("cost_first", C.c_double), ("cost_last", C.c_double), ("max_update", C.c_double), ("lambda_", C.c_double),
+                ("iterations", C.c_int32), ("status", C.c_int32), ("n_params", C.c_int32), ("n_border", C.c_int32)]
+
+
+PGO_CONVERGED, PGO_MAX_ITERS, PGO_SOLVE_FAILED, PGO_HALF_TURN = 0, 1, 2, 3      # lcm_pgo_status
+PGO_LOOP_AS_WRITTEN, PGO_LOOP_INVERTED = 0, 1                                   # lcm_pgo_loop_direction
+PGO_MAX_POSES, PGO_MAX_LOOPS = 4096, 8
+
+
 class LoParams(C.Structure):
     """lcm_lo_params: the rounds of the RANSAC's local optimisation and their threshold multipliers (96 bytes)."""
     _fields_ = [("rounds", C.c_int32), ("seeds", C.c_int32), ("mult", C.c_double * 8), ("reserved", C.c_uint32 * 6)]
@@ -146,6 +163,9 @@ assert EPI_RESULT_DTYPE.itemsize == C.sizeof(EpiResult) == 88 and C.sizeof(EpiPa
 POSE_RESULT_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("counts", "<i4", (4,)), ("n_used", "<i4"), ("n_good", "<i4"),
                               ("choice", "<i4"), ("status", "<i4")])          # lcm_pose_result
 assert POSE_RESULT_DTYPE.itemsize == C.sizeof(PoseResult) == 128 and C.sizeof(PoseParams) == 32
+PGO_POSE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,))])             # lcm_pgo_pose
+PGO_EDGE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("weight", "<f8"), ("from", "<i4"), ("to", "<i4")])    # lcm_pgo_edge
+assert PGO_POSE_DTYPE.itemsize == 96 and PGO_EDGE_DTYPE.itemsize == 112 and C.sizeof(PgoParams) == 64 and C.sizeof(PgoInfo) == 48
 LO_INFO_DTYPE = np.dtype([("seed_iter", "<i4"), ("round", "<i4"), ("n_inliers_ransac", "<i4"), ("status", "<i4")])    # lcm_lo_info
 assert LO_INFO_DTYPE.itemsize == C.sizeof(LoInfo) == 16 and C.sizeof(LoParams) == 96
 assert SCORE_DTYPE.itemsize == C.sizeof(Score) == 8
@@ -246,6 +266,14 @@ _SIGNATURES = {
     "lcm_pose_db_detect_loops": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(RatioLoopParams),
                                             C.POINTER(EpiParams), C.POINTER(PoseParams), _vp, C.c_size_t, C.POINTER(C.c_size_t),
                                             C.POINTER(C.c_size_t), _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_int, _i32p]),
+    "lcm_pgo_params_default": (None, [C.POINTER(PgoParams)]),
+    "lcm_pgo_optimize": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(PgoParams), _vp, C.POINTER(PgoInfo)]),
+    "lcm_pgo_step": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(PgoParams), _vp, _vp, _vp, _vp, C.POINTER(PgoInfo)]),
+    "lcm_pgo_build_graph": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.POINTER(PgoParams), _vp, C.c_int, _i32p]),
+    "lcm_pgo_rotation_drift": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(C.c_double)]),
+    "lcm_pgo_linear_correct": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "lcm_pgo_close_loop": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(PoseResult), C.POINTER(PgoParams), _vp,
+                                      C.POINTER(PgoInfo)]),
     "lcm_query_scores": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _i32p]),
     "lcm_query_submit": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _i32p]),
     "lcm_query_collect": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i32p]),
@@ -426,6 +454,75 @@ def pose_best(epi_results, pose_results, ep: EpiParams, pp: Optional[PoseParams]
     _check(load_library().lcm_pose_best(er.ctypes.data_as(_vp), pr.ctypes.data_as(_vp), len(er), C.byref(ep),
                                         None if pp is None else C.byref(pp), floor_inliers, C.byref(best)))
     return best.value
+
+
+def default_pgo_params(**over) -> PgoParams:
+    """lcm_pgo_params_default (eps 1e-6, damping 1e-4, min_update 1e-6, loop_weight 10, max_iters 20, loop_direction 0) with any
+    field given by name."""
+    p = PgoParams()
+    load_library().lcm_pgo_params_default(C.byref(p))
+    for k, v in over.items():
+        if k not in ("eps", "damping", "min_update", "loop_weight", "max_iters", "loop_direction"):
+            raise TypeError(f"lcm_pgo_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def pgo_poses(R, t) -> np.ndarray:
+    """PGO_POSE_DTYPE[n] from rotations [n, 3, 3] and translations [n, 3]."""
+    R = np.asarray(R, np.float64)
+    out = np.zeros(len(R), PGO_POSE_DTYPE)
+    out["R"] = R.reshape(len(R), 9)
+    out["t"] = np.asarray(t, np.float64).reshape(len(R), 3)
+    return out
+
+
+def pgo_edges(R, t, weight, ends) -> np.ndarray:
+    """PGO_EDGE_DTYPE[n] from rotations [n, 3, 3], translations [n, 3], weights [n] and (from, to) pairs [n, 2]."""
+    R = np.asarray(R, np.float64)
+    out = np.zeros(len(R), PGO_EDGE_DTYPE)
+    out["R"] = R.reshape(len(R), 9)
+    out["t"] = np.asarray(t, np.float64).reshape(len(R), 3)
+    out["weight"] = weight
+    ends = np.asarray(ends, np.int32).reshape(len(R), 2)
+    out["from"], out["to"] = ends[:, 0], ends[:, 1]
+    return out
+
+
+def _pgo_graph(poses, valid):
+    p = np.ascontiguousarray(poses, PGO_POSE_DTYPE)
+    v = None if valid is None else np.ascontiguousarray(valid, np.uint8)
+    assert v is None or len(v) == len(p)
+    return p, v
+
+
+def pgo_build_graph(poses, past: int, curr: int, R_loop, t_loop, pp: Optional[PgoParams] = None, valid=None) -> np.ndarray:
+    """lcm_pgo_build_graph (host only): the sequential edges of the valid poses and the loop edge past -> curr, PGO_EDGE_DTYPE[n]."""
+    p, v = _pgo_graph(poses, valid)
+    Rl, tl = np.ascontiguousarray(R_loop, np.float64).reshape(9), np.ascontiguousarray(t_loop, np.float64).reshape(3)
+    out = np.zeros(max(len(p), 1), PGO_EDGE_DTYPE)
+    n = C.c_int32(0)
+    _check(load_library().lcm_pgo_build_graph(_ptr(p), _ptr(v), len(p), past, curr, _ptr(Rl), _ptr(tl), _ref(pp), _ptr(out), len(out),
+                                              C.byref(n)))
+    return out[:n.value]
+
+
+def pgo_rotation_drift(poses, past: int, curr: int, R_loop) -> float:
+    """lcm_pgo_rotation_drift (host only): |log(R_loop (R_curr R_past^T)^T)| in radians."""
+    p, _ = _pgo_graph(poses, None)
+    Rl = np.ascontiguousarray(R_loop, np.float64).reshape(9)
+    angle = C.c_double(-1.0)
+    _check(load_library().lcm_pgo_rotation_drift(_ptr(p), len(p), past, curr, _ptr(Rl), C.byref(angle)))
+    return angle.value
+
+
+def pgo_linear_correct(poses, past: int, curr: int, R_loop, valid=None) -> np.ndarray:
+    """lcm_pgo_linear_correct (host only): the reference's simplePoseCorrection, PGO_POSE_DTYPE[n]."""
+    p, v = _pgo_graph(poses, valid)
+    Rl = np.ascontiguousarray(R_loop, np.float64).reshape(9)
+    out = np.zeros(max(len(p), 1), PGO_POSE_DTYPE)
+    _check(load_library().lcm_pgo_linear_correct(_ptr(p), _ptr(v), len(p), past, curr, _ptr(Rl), _ptr(out)))
+    return out[:len(p)]
 
 
 def _point_pairs(pts) -> np.ndarray:
@@ -1161,6 +1258,42 @@ class Matcher:
     def pose_best(epi_results, pose_results, ep: EpiParams, pp: Optional[PoseParams] = None, floor_inliers: int = -1) -> int:
         """lcm_pose_best (host only): see capi.pose_best."""
         return pose_best(epi_results, pose_results, ep, pp, floor_inliers)
+
+    # -- closing the loop: pose-graph Gauss-Newton correction (lcm_pgo_*) --
+    def pgo_optimize(self, poses, edges, pp: Optional[PgoParams] = None, valid=None):
+        """optimizePoseGraph over PGO_POSE_DTYPE[n] and PGO_EDGE_DTYPE[m] (valid: uint8[n] or None = all): (PGO_POSE_DTYPE[n],
+        PgoInfo)."""
+        p, v = _pgo_graph(poses, valid)
+        e = np.ascontiguousarray(edges, PGO_EDGE_DTYPE)
+        out = np.zeros(max(len(p), 1), PGO_POSE_DTYPE)
+        info = PgoInfo()
+        _check(self._lib.lcm_pgo_optimize(self._h, _ptr(p), _ptr(v), len(p), _ptr(e), len(e), _ref(pp), _ptr(out), C.byref(info)))
+        return out[:len(p)], info
+
+    def pgo_step(self, poses, edges, pp: Optional[PgoParams] = None, valid=None):
+        """The test seam, one iteration: (params float64[n, 6] before the update, residuals float64[m, 6], Jacobian
+        float64[m, 6, 12], dp float64[n - 1, 6], PgoInfo)."""
+        p, v = _pgo_graph(poses, valid)
+        e = np.ascontiguousarray(edges, PGO_EDGE_DTYPE)
+        n, m = len(p), len(e)
+        params, res, jac, dp = np.zeros((max(n, 1), 6)), np.zeros((max(m, 1), 6)), np.zeros((max(m, 1), 6, 12)), np.zeros((max(n - 1, 1), 6))
+        info = PgoInfo()
+        _check(self._lib.lcm_pgo_step(self._h, _ptr(p), _ptr(v), n, _ptr(e), m, _ref(pp), _ptr(params), _ptr(res), _ptr(jac), _ptr(dp),
+                                      C.byref(info)))
+        return params[:n], res[:m], jac[:m], dp[:max(n - 1, 0)], info
+
+    def pgo_close_loop(self, poses, past: int, curr: int, pose_result, pp: Optional[PgoParams] = None, valid=None):
+        """lcm_pgo_build_graph on the relative pose (a PoseResult or a POSE_RESULT_DTYPE record) + lcm_pgo_optimize:
+        (PGO_POSE_DTYPE[n], PgoInfo).  pp.loop_direction says how the pose becomes the loop edge."""
+        p, v = _pgo_graph(poses, valid)
+        if isinstance(pose_result, PoseResult):
+            pr = pose_result
+        else:
+            pr = PoseResult.from_buffer_copy(np.ascontiguousarray(pose_result, POSE_RESULT_DTYPE).reshape(1)[0].tobytes())
+        out = np.zeros(max(len(p), 1), PGO_POSE_DTYPE)
+        info = PgoInfo()
+        _check(self._lib.lcm_pgo_close_loop(self._h, _ptr(p), _ptr(v), len(p), past, curr, C.byref(pr), _ref(pp), _ptr(out), C.byref(info)))
+        return out[:len(p)], info
 
     # -- loop search -------------------------------------------------------------------------------
     def query_scores(self, query, query_frame_id: int) -> Tuple[np.ndarray, np.ndarray]:

@@ -11,6 +11,7 @@
 //   lcm_epi.cpp        essential-matrix RANSAC over the loop candidates' correspondences (lcm_epi_*)
 //   lcm_pose.cpp       relative pose of the verified candidates and the best loop (lcm_pose_*)
 //   lcm_lo.cpp         local optimisation of the RANSAC's best hypotheses (lcm_lo_*)
+//   lcm_pgo.cpp        pose-graph Gauss-Newton correction of the closed loop (lcm_pgo_*)
 //   lcm_verify.cpp     the three as one staged pipeline over a VerifyPlan (lcm_verify_host.h); the store's and the host-list forms
 // Not installed; the public surface is include/lcm.h.
 #pragma once
@@ -298,6 +299,12 @@ struct lcm_handle {
         double* d_models = nullptr;   size_t d_models_n = 0;     // the refit seam: 64 x 9 in, 64 x 9 out
         int32_t* d_seam = nullptr;    size_t d_seam_n = 0;       // ... and 64 counts + 64 statuses
     } lo;
+    // pose-graph correction (lcm_pgo.cpp): one graph's [poses | edges | table | valid | returned poses | state] as bytes, and
+    // every array of doubles of a run (parameters, residuals, Jacobian, the blocks of the normal equations and of their factor)
+    struct PgoScratch {
+        uint8_t* d_in = nullptr;      size_t d_in_n = 0;
+        double* d_work = nullptr;     size_t d_work_n = 0;
+    } pgo;
     lcm_launch_info info{};
     bool info_pending = false;
 };

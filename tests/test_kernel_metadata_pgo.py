@@ -1,0 +1,100 @@
+"""Code-object metadata of the pose-graph correction (lcm_pgo.hip; hipcc cross-compiles gfx950 without a GPU): exactly the
+kernels the file's header names, without scratch memory or spills, each within the VGPR and LDS budget the header states; and
+from the source text: exp, log, the edge residual and the 6 x 6 Cholesky defined once in lcm_pgo_device.h and called, not
+restated, by the kernels, no floating-point atomic, and the other kernel files' kernel lists as they were.  Metadata fields and
+source structure only."""
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "slam-loop-closing_amd", "csrc")
+HIPCC = "/opt/rocm/bin/hipcc"
+FIELDS = ("private_segment_fixed_size", "vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "group_segment_fixed_size")
+# kernel -> (VGPRs, LDS bytes), the file header's budget.  The two single-workgroup kernels may use what one wave per SIMD has;
+# the grid kernels stay at 128 and below (four waves per SIMD and more).
+BUDGET = {"k_pgo_params": (128, 0), "k_pgo_linearise": (128, 0), "k_pgo_assemble": (64, 0), "k_pgo_sweep": (256, 2048),
+          "k_pgo_schur": (64, 0), "k_pgo_finish": (128, 2824), "k_pgo_writeback": (128, 0)}
+
+
+def kernels_of(src):
+    return re.findall(r"__global__[^\n]*\bvoid\s+(\w+)\s*\(", src)
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+def test_kernels_use_no_scratch_and_fit_their_budgets(tmp_path):
+    out = tmp_path / "lcm_pgo.s"
+    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-x", "hip",
+                           os.path.join(CSRC, "lcm_pgo.hip"), "-o", str(out)], stderr=subprocess.DEVNULL)
+    text = out.read_text()
+    meta = text[text.index("amdhsa.kernels:"):]
+    ks = {}
+    for block in re.split(r"\n  - \.a", meta)[1:]:
+        name = re.search(r"\.name:\s+(\S+)", block).group(1)
+        short = re.search(r"(k_pgo_[a-z]+)E", name).group(1)
+        ks[short] = {k: int(re.search(rf"\.{k}:\s+(\d+)", block).group(1)) for k in FIELDS}
+    assert sorted(ks) == sorted(BUDGET)
+    for name, m in sorted(ks.items()):
+        print(name, m)
+        vgprs, lds = BUDGET[name]
+        assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0, (name, m)
+        assert m["vgpr_count"] <= vgprs and m["group_segment_fixed_size"] <= lds, (name, m)
+        assert (m["group_segment_fixed_size"] > 0) == (lds > 0), (name, m)
+
+
+def test_the_header_names_every_kernel_and_states_the_budget():
+    src = open(os.path.join(CSRC, "lcm_pgo.hip")).read()
+    head = src[: src.index("#include")]
+    assert sorted(kernels_of(src)) == sorted(BUDGET)
+    for name in BUDGET:
+        assert re.search(rf"^// {name}\s", head, flags=re.M), name
+    budget = re.sub(r"\s+", " ", head[head.index("// Budget"):].replace("\n//", " "))
+    assert "no scratch, no spills" in budget
+    for names, (vgprs, lds) in ((("k_pgo_params", "k_pgo_linearise", "k_pgo_writeback"), (128, 0)), (("k_pgo_assemble",), (64, 0)),
+                                (("k_pgo_sweep",), (256, 2048)), (("k_pgo_schur",), (64, 0)), (("k_pgo_finish",), (128, 2824))):
+        what = f"at most {vgprs} VGPRs and " + (f"{lds} bytes of LDS" if lds else "no LDS")
+        listed = ", ".join(names[:-1]) + (" and " if len(names) > 1 else "") + names[-1]
+        assert f"{listed} {what}" in budget, (listed, what)
+        assert all(BUDGET[n] == (vgprs, lds) for n in names)
+    make = open(os.path.join(CSRC, "Makefile")).read()
+    assert "lcm_pgo.hip" in make and "lcm_pgo.cpp" in make and "lcm_pgo_device.h" in make and "lcm_pgo_host.h" in make
+
+
+def test_the_arithmetic_exists_once_and_is_called_from_the_kernels():
+    src = open(os.path.join(CSRC, "lcm_pgo.hip")).read()
+    dev = open(os.path.join(CSRC, "lcm_pgo_device.h")).read()
+    for fn in ("void pgo_exp(", "bool pgo_log(", "bool pgo_edge_residual(", "bool pgo_chol6(", "void pgo_lower_solve6(", "void pgo_upper_solve6("):
+        assert dev.count(fn) == 1 and fn not in src, fn
+    dev_code = re.sub(r"//[^\n]*", "", dev)
+    assert dev_code.count("atan2(") == 1 and dev_code.count("cos(theta)") == 1 and dev_code.count("sin(theta)") == 1
+    code = re.sub(r"//[^\n]*", "", src)                     # the kernels' text without its comments
+    assert code.count("pgo_edge_residual(") == 3            # the residual itself, +eps, -eps
+    assert code.count("pgo_exp(") == 2 and code.count("pgo_log(") == 1          # the poses' exp (linearise, write-back), the poses' log
+    assert code.count("pgo_chol6(") == 1 and code.count("pgo_lower_solve6(") == 2 and code.count("pgo_upper_solve6(") == 1
+    # no trigonometry, no square root of a pivot block and no rotation formula of the kernel file's own
+    words = set(re.findall(r"\b\w+\b", code))
+    assert not words & {"atan2", "sin", "cos", "acos", "asin", "sincos", "theta"}
+    # no floating-point atomics: no atomic at all
+    assert not re.search(r"atomic", code, flags=re.I) and not re.search(r"atomic", dev, flags=re.I)
+    assert "asm" not in words and "__builtin_amdgcn_global_atomic_fadd_f64" not in code
+    # the host runs none of it but through lcm_pgo_host.h's host-only calls
+    host = re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, "lcm_pgo.cpp")).read())
+    for fn in ("pgo_exp(", "pgo_log(", "pgo_edge_residual(", "pgo_chol6("):
+        assert fn not in host, fn
+    assert "#pragma clang fp contract(off)" in dev and "fp contract(off)" in src
+
+
+def test_the_other_kernel_files_keep_their_kernels():
+    want = {"lcm_pose.hip": ["k_pose_recover"], "lcm_lo.hip": ["k_lo_select", "k_lo_refine"], "lcm_epi.hip": ["k_epi_solve", "k_epi_score", "k_epi_mask"]}
+    every = []
+    for f in sorted(os.listdir(CSRC)):
+        if f.endswith(".hip"):
+            ks = kernels_of(open(os.path.join(CSRC, f)).read())
+            every += ks
+            if f in want:
+                assert sorted(ks) == sorted(want[f]), (f, ks)
+            if f != "lcm_pgo.hip":
+                assert not any("pgo" in k for k in ks) and "lcm_pgo" not in open(os.path.join(CSRC, f)).read(), f
+    assert len(every) == len(set(every))
