@@ -752,6 +752,150 @@ LCM_API int  lcm_pgo_linear_correct(const lcm_pgo_pose* poses, const uint8_t* va
 LCM_API int  lcm_pgo_close_loop(lcm_handle* h, const lcm_pgo_pose* poses, const uint8_t* valid, int n_poses, int past, int curr,
                                 const lcm_pose_result* pr, const lcm_pgo_params* pp, lcm_pgo_pose* poses_out, lcm_pgo_info* info);
 
+/* ---- after the loop: alternating bundle adjustment and outlier removal on the device -------------------------------------- */
+/* src/main.cpp:1494-1669: the loop's inlier matches become observations of existing points (:1494-1513), the mean
+ * reprojection error (:1543, computeReprojectionError :871-896), alternatingBundleAdjustment (:1546, :905-943: the pose-only
+ * Gauss-Newton step refineCameraPoseGN :632-743 and the point-only step refinePointGN :757-858), the outlier flags and the
+ * compaction (:1563-1659) and the second adjustment (:1666).  With the points fixed every camera is independent of every other,
+ * and with the poses fixed so is every point: a phase runs all its elements at once and gives what the reference's sequential
+ * loops over camIdx / ptIdx give (lcm_ba_device.h, lcm_ba.hip).  In double, every product and sum rounded on its own:
+ *   projection   (:149-165) Xc = (R Xw) + t, each row of the product summed left to right; u = ((fx x) / z) + cx,
+ *                v = ((fy y) / z) + cy.  There is no test on z, as in the reference.  residual = projection - pixel.
+ *   cameras      per valid camera with at least min_cam_obs observations: p = (log R, t), exp and log those of the pose graph
+ *                above, the same stated departure from cv::Rodrigues below a sine of 1e-5 included.  The camera's observations
+ *                are taken in ascending index of the caller's list.  Each iteration: the residuals r; the six columns
+ *                (r(p + eps e_k) - r(p - eps e_k)) * (0.5 / eps), the rotation rebuilt by exp once per camera, iteration and
+ *                parameter vector; H = J^T J, g = J^T r, H_kk += damping (absolute, not scaled by the trace as the pose
+ *                graph's), H dp = -g by Cholesky.  A pivot that is not > 0 (NaN included) ends the element BEFORE the update as
+ *                LCM_BA_SOLVE_FAILED; otherwise p += dp, and max |dp_k| < min_update ends it after the update as
+ *                LCM_BA_CONVERGED, inner_iters updates without that as LCM_BA_MAX_ITERS.
+ *   write-back   R = exp(p[0..3)), t = p[3..6) for every status but LCM_BA_HALF_TURN: the reference writes paramsToPose(p) back
+ *                even when no update was applied.  A camera whose R has no rotation vector (LCM_BA_HALF_TURN) and a skipped one
+ *                (LCM_BA_SKIPPED: fewer than min_cam_obs observations, or valid[i] == 0) come back byte for byte.
+ *   points       the same with p = (x, y, z), three columns and a 3 x 3 system; a point with fewer than min_point_obs
+ *                observations is LCM_BA_SKIPPED and comes back byte for byte, every other point as its p.
+ *   sums         the order of the sums in H and g over an element's observations is fixed and stated in lcm_ba.hip's header;
+ *                the same call gives the same bytes, and an element's k-th iteration depends neither on min_update nor on
+ *                inner_iters.
+ *   mean error   (:871-896) the sum of sqrt(dx dx + dy dy) over all observations in a fixed order, divided by their number;
+ *                0.0 for no observation.
+ *   outliers     (:1563-1619) per point: an observation with Xc.z <= 0 flags the point and does not enter the maximum; otherwise
+ *                its error enters the point's max_err, and err > outlier_px flags the point.  The centroid of the valid cameras'
+ *                centres -R^T t and the largest distance of a centre from it are computed on the host;
+ *                threshold = max(min_spread, spread_factor x that distance); a point farther than the threshold from the
+ *                centroid is flagged.
+ * A map is (poses, valid, n_poses, points, n_points, obs, n_obs): valid is one byte per pose, NULL = all valid, and an invalid
+ * pose's contents are not read.  Refused by every call over a map with LCM_ERR_INVALID_ARG before anything is launched or
+ * written: a NULL buffer, pp == NULL (the camera matrix has no default), n_poses < 1, n_points < 1, n_obs < 0, an observation
+ * index out of range, an observation of an invalid camera, a non-finite double in a valid pose, a point or an observation, a
+ * pose R with max |R R^T - I| > 1e-6 or a negative determinant, a bad pp field; LCM_ERR_CAPACITY above the limits, decided from
+ * the counts before any buffer is read.  Ordered on the handle's stream and finished on return; lcm_last_launch_info:
+ * kernel_ms, launches, pairs = n_obs. */
+#define LCM_BA_MAX_CAMERAS 4096
+#define LCM_BA_MAX_POINTS 16777216
+#define LCM_BA_MAX_OBS 16777216
+#define LCM_BA_MAX_ITERS_PER_LOOP 16
+typedef struct lcm_ba_point { double x, y, z; } lcm_ba_point;                                 /* 24 bytes */
+typedef struct lcm_ba_obs { int32_t cam, point; double u, v; } lcm_ba_obs;                    /* 24 bytes */
+typedef enum lcm_ba_status { LCM_BA_CONVERGED = 0, LCM_BA_MAX_ITERS = 1, LCM_BA_SOLVE_FAILED = 2, LCM_BA_HALF_TURN = 3,
+                             LCM_BA_SKIPPED = 4 } lcm_ba_status;
+typedef struct lcm_ba_elem_info {     /* one per camera or per point */
+    double last_update;               /* max |dp_k| of the last update applied, 0 if none */
+    double cost;                      /* r . r of the last linearisation made (a failed solve's included), 0 if none */
+    int32_t iterations;               /* updates applied */
+    int32_t status;                   /* lcm_ba_status */
+} lcm_ba_elem_info;                   /* 24 bytes */
+typedef struct lcm_ba_params {        /* defaults = the reference's constants */
+    double fx, fy, cx, cy;            /* the camera matrix K; the defaults leave it zero: fx <= 0 or fy <= 0 is LCM_ERR_INVALID_ARG */
+    double eps;                       /* 1e-6: the central difference's step, finite and > 0 */
+    double damping;                   /* 1e-3: added to H's diagonal, finite and >= 0 */
+    double min_update;                /* 1e-6: finite and >= 0; 0 never converges (every iteration runs) */
+    double outlier_px;                /* 5.0:  OUTLIER_REPROJ_THRESHOLD */
+    double min_spread;                /* 10.0: the distance threshold's floor */
+    double spread_factor;             /* 5.0:  ... and its multiple of the cameras' spread */
+    int32_t outer_iters;              /* 5, in [1, 16]: lcm_ba_optimize's (camera phase, point phase, mean error) rounds */
+    int32_t inner_iters;              /* 5, in [1, 16]: Gauss-Newton iterations per element and phase */
+    int32_t min_cam_obs;              /* 10 */
+    int32_t min_point_obs;            /* 2 */
+    int32_t reserved[4];              /* ignored */
+} lcm_ba_params;                      /* 112 bytes */
+typedef struct lcm_ba_info {
+    double mean_error[17];            /* [0] before the run, [k] after outer iteration k; unused entries are 0 */
+    int32_t outer_iters;              /* rounds run */
+    int32_t cameras[5];               /* cameras per lcm_ba_status after the last outer iteration */
+    int32_t points[5];                /* points per lcm_ba_status after the last outer iteration */
+    int32_t reserved;
+} lcm_ba_info;                        /* 184 bytes */
+typedef struct lcm_ba_map_report {    /* lcm_ba_refine_map */
+    double error_before, error_after; /* :1543, :1554: around the first adjustment */
+    double error_filtered, error_final;   /* :1663, :1668: around the second */
+    double threshold;                 /* the outlier pass's distance threshold */
+    int32_t n_outliers;               /* points flagged */
+    int32_t n_points, n_obs;          /* what the compaction kept */
+    int32_t reserved;
+} lcm_ba_map_report;                  /* 56 bytes */
+LCM_API void lcm_ba_params_default(lcm_ba_params* p);
+/* computeReprojectionError: *mean, and with obs_err != NULL one error per observation (n_obs doubles) in the caller's order. */
+LCM_API int  lcm_ba_error(lcm_handle* h, const lcm_pgo_pose* poses, const uint8_t* valid, int n_poses, const lcm_ba_point* points,
+                          int n_points, const lcm_ba_obs* obs, int n_obs, const lcm_ba_params* pp, double* mean, double* obs_err);
+/* One phase: every camera (every point) at once.  poses_out: n_poses records (points_out: n_points), may alias the input;
+ * info: one record per camera (per point).  outer_iters is not used. */
+LCM_API int  lcm_ba_refine_cameras(lcm_handle* h, const lcm_pgo_pose* poses, const uint8_t* valid, int n_poses, const lcm_ba_point* points,
+                                   int n_points, const lcm_ba_obs* obs, int n_obs, const lcm_ba_params* pp, lcm_pgo_pose* poses_out,
+                                   lcm_ba_elem_info* info);
+LCM_API int  lcm_ba_refine_points(lcm_handle* h, const lcm_pgo_pose* poses, const uint8_t* valid, int n_poses, const lcm_ba_point* points,
+                                  int n_points, const lcm_ba_obs* obs, int n_obs, const lcm_ba_params* pp, lcm_ba_point* points_out,
+                                  lcm_ba_elem_info* info);
+/* The test seam: one linearisation of every element through the kernels the phases launch (pp is checked whole; inner_iters and
+ * outer_iters are not used).  r: 2 n_obs doubles and J: n_obs x 2 x 6 (points: n_obs x 2 x 3) row-major, in the caller's order,
+ * zero for an observation of an element that was not linearised; H: n_poses x 6 x 6 (n_points x 3 x 3) BEFORE damping, g and dp:
+ * 6 per camera (3 per point), zero for such an element, dp zero after a failed solve; info as the phase's with inner_iters = 1. */
+LCM_API int  lcm_ba_step_cameras(lcm_handle* h, const lcm_pgo_pose* poses, const uint8_t* valid, int n_poses, const lcm_ba_point* points,
+                                 int n_points, const lcm_ba_obs* obs, int n_obs, const lcm_ba_params* pp, double* r, double* J, double* H,
+                                 double* g, double* dp, lcm_ba_elem_info* info);
+LCM_API int  lcm_ba_step_points(lcm_handle* h, const lcm_pgo_pose* poses, const uint8_t* valid, int n_poses, const lcm_ba_point* points,
+                                int n_points, const lcm_ba_obs* obs, int n_obs, const lcm_ba_params* pp, double* r, double* J, double* H,
+                                double* g, double* dp, lcm_ba_elem_info* info);
+/* alternatingBundleAdjustment: the mean error, then outer_iters x (camera phase, point phase, mean error), every launch enqueued
+ * back to back on the handle's stream; only poses_out, points_out, the element infos of the last round (cam_info: n_poses,
+ * pt_info: n_points; each may be NULL) and *info come back.  The outputs may alias the inputs. */
+LCM_API int  lcm_ba_optimize(lcm_handle* h, const lcm_pgo_pose* poses, const uint8_t* valid, int n_poses, const lcm_ba_point* points,
+                             int n_points, const lcm_ba_obs* obs, int n_obs, const lcm_ba_params* pp, lcm_pgo_pose* poses_out,
+                             lcm_ba_point* points_out, lcm_ba_elem_info* cam_info, lcm_ba_elem_info* pt_info, lcm_ba_info* info);
+/* The outlier flags: flags (one byte per point, 1 = outlier) and max_err (one double per point, may be NULL), *threshold (may
+ * be NULL) and *n_outliers. */
+LCM_API int  lcm_ba_outliers(lcm_handle* h, const lcm_pgo_pose* poses, const uint8_t* valid, int n_poses, const lcm_ba_point* points,
+                             int n_points, const lcm_ba_obs* obs, int n_obs, const lcm_ba_params* pp, uint8_t* flags, double* max_err,
+                             double* threshold, int* n_outliers);
+/* Host only (:1633-1659): the points with flags[i] == 0 in order, the observations of such points in order with the new point
+ * index, old_to_new (n_points entries, -1 for a removed point; may be NULL).  *n_points_out and *n_obs_out are the counts; if
+ * they exceed cap_points / cap_obs: LCM_ERR_CAPACITY and nothing else is written.  An observation's point index out of range is
+ * LCM_ERR_INVALID_ARG.  The outputs must not alias the inputs. */
+LCM_API int  lcm_ba_compact(const lcm_ba_point* points, int n_points, const lcm_ba_obs* obs, int n_obs, const uint8_t* flags,
+                            lcm_ba_point* points_out, int cap_points, lcm_ba_obs* obs_out, int cap_obs, int32_t* old_to_new,
+                            int* n_points_out, int* n_obs_out);
+/* Host only (:1496-1513).  matches / mask (n_matches records and bytes): the match list and the mask of the best candidate as
+ * lcm_pose_db_detect_loops returns them (query_idx: the current frame's keypoint, train_idx: the past frame's).  past_table
+ * (n_past_kp entries): the past frame's keypoint -> point index, -1 = none; curr_table (n_curr_kp entries): the current
+ * frame's, updated in place; curr_kp: the current frame's keypoints, n_curr_kp (x, y) pairs of floats.  For every masked match
+ * whose past keypoint has a point, in order, {curr, point, pixel} is appended at obs[n_obs ...] (obs has room for cap records
+ * in all) and curr_table[query_idx] = point.  *n_added = their number; n_obs + *n_added > cap: LCM_ERR_CAPACITY and nothing is
+ * written but *n_added.  An index outside its list or a table entry outside [-1, n_points) is LCM_ERR_INVALID_ARG. */
+LCM_API int  lcm_ba_add_loop_observations(const lcm_dmatch* matches, const uint8_t* mask, int n_matches, const int32_t* past_table,
+                                          int n_past_kp, int32_t* curr_table, const float* curr_kp, int n_curr_kp, int curr,
+                                          int n_points, lcm_ba_obs* obs, int n_obs, int cap, int* n_added);
+/* :1543-1669 in one call: lcm_ba_error, lcm_ba_optimize with pp->outer_iters, lcm_ba_outliers, lcm_ba_compact, lcm_ba_error,
+ * lcm_ba_optimize with second_outer_iters (<= 0: 3, the reference's; at most 16), lcm_ba_error.  poses_out: n_poses records;
+ * points_out: n_points; obs_out: n_obs; old_to_new: n_points entries or NULL; the outputs must not alias the inputs.  The kept
+ * counts are report->n_points and report->n_obs.  If the outlier pass keeps no point the call ends after the compaction with
+ * error_filtered = error_final = 0.  The inputs are refused before anything is written; should the first adjustment leave a
+ * non-finite value behind (an element that diverged), the later steps refuse it with LCM_ERR_INVALID_ARG after poses_out has
+ * been written, and *report is not.  lcm_last_launch_info describes the last step that launched. */
+LCM_API int  lcm_ba_refine_map(lcm_handle* h, const lcm_pgo_pose* poses, const uint8_t* valid, int n_poses, const lcm_ba_point* points,
+                               int n_points, const lcm_ba_obs* obs, int n_obs, const lcm_ba_params* pp, int second_outer_iters,
+                               lcm_pgo_pose* poses_out, lcm_ba_point* points_out, lcm_ba_obs* obs_out, int32_t* old_to_new,
+                               lcm_ba_map_report* report);
+
 /* ---- loop search against the stored database --------------------------------------------------------- */
 /* Score `query` (id query_frame_id) against every stored frame with query_frame_id - id >= min_gap, ascending
  * slot order.  out_scores / out_frame_ids need room for lcm_db_size() records. */

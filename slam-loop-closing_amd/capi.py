@@ -108,6 +108,32 @@ PGO_LOOP_AS_WRITTEN, PGO_LOOP_INVERTED = 0, 1                                   
 PGO_MAX_POSES, PGO_MAX_LOOPS = 4096, 8
 
 
+class BaParams(C.Structure):
+    """lcm_ba_params: the camera matrix, the Gauss-Newton steps' constants, the outlier pass's thresholds, the iteration counts
+    and the smallest observation counts of an adjusted camera and point (112 bytes)."""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("eps", C.c_double),
+                ("damping", C.c_double), ("min_update", C.c_double), ("outlier_px", C.c_double), ("min_spread", C.c_double),
+                ("spread_factor", C.c_double), ("outer_iters", C.c_int32), ("inner_iters", C.c_int32), ("min_cam_obs", C.c_int32),
+                ("min_point_obs", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class BaInfo(C.Structure):
+    """lcm_ba_info: the mean error before the run and after every outer iteration, the rounds, the cameras and the points per
+    status after the last round (184 bytes)."""
+    _fields_ = [("mean_error", C.c_double * 17), ("outer_iters", C.c_int32), ("cameras", C.c_int32 * 5), ("points", C.c_int32 * 5),
+                ("reserved", C.c_int32)]
+
+
+class BaMapReport(C.Structure):
+    """lcm_ba_map_report: lcm_ba_refine_map's four errors, the distance threshold, the outliers, what was kept (56 bytes)."""
+    _fields_ = [("error_before", C.c_double), ("error_after", C.c_double), ("error_filtered", C.c_double), ("error_final", C.c_double),
+                ("threshold", C.c_double), ("n_outliers", C.c_int32), ("n_points", C.c_int32), ("n_obs", C.c_int32), ("reserved", C.c_int32)]
+
+
+BA_CONVERGED, BA_MAX_ITERS, BA_SOLVE_FAILED, BA_HALF_TURN, BA_SKIPPED = 0, 1, 2, 3, 4      # lcm_ba_status
+BA_MAX_CAMERAS, BA_MAX_POINTS, BA_MAX_OBS, BA_MAX_ITERS_PER_LOOP = 4096, 1 << 24, 1 << 24, 16
+
+
 class LoParams(C.Structure):
     """lcm_lo_params: the rounds of the RANSAC's local optimisation and their threshold multipliers (96 bytes)."""
     _fields_ = [("rounds", C.c_int32), ("seeds", C.c_int32), ("mult", C.c_double * 8), ("reserved", C.c_uint32 * 6)]
@@ -166,6 +192,11 @@ assert POSE_RESULT_DTYPE.itemsize == C.sizeof(PoseResult) == 128 and C.sizeof(Po
 PGO_POSE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,))])             # lcm_pgo_pose
 PGO_EDGE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("weight", "<f8"), ("from", "<i4"), ("to", "<i4")])    # lcm_pgo_edge
 assert PGO_POSE_DTYPE.itemsize == 96 and PGO_EDGE_DTYPE.itemsize == 112 and C.sizeof(PgoParams) == 64 and C.sizeof(PgoInfo) == 48
+BA_POINT_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8")])                                     # lcm_ba_point
+BA_OBS_DTYPE = np.dtype([("cam", "<i4"), ("point", "<i4"), ("u", "<f8"), ("v", "<f8")])                     # lcm_ba_obs
+BA_ELEM_INFO_DTYPE = np.dtype([("last_update", "<f8"), ("cost", "<f8"), ("iterations", "<i4"), ("status", "<i4")])    # lcm_ba_elem_info
+assert BA_POINT_DTYPE.itemsize == 24 and BA_OBS_DTYPE.itemsize == 24 and BA_ELEM_INFO_DTYPE.itemsize == 24
+assert C.sizeof(BaParams) == 112 and C.sizeof(BaInfo) == 184 and C.sizeof(BaMapReport) == 56
 LO_INFO_DTYPE = np.dtype([("seed_iter", "<i4"), ("round", "<i4"), ("n_inliers_ransac", "<i4"), ("status", "<i4")])    # lcm_lo_info
 assert LO_INFO_DTYPE.itemsize == C.sizeof(LoInfo) == 16 and C.sizeof(LoParams) == 96
 assert SCORE_DTYPE.itemsize == C.sizeof(Score) == 8
@@ -179,6 +210,8 @@ _lib = None
 _u8p = C.POINTER(C.c_uint8)
 _i32p = C.POINTER(C.c_int32)
 _vp = C.c_void_p
+# a map as the lcm_ba_* calls take it: handle, poses, valid, n_poses, points, n_points, obs, n_obs, params
+_BA_MAP = [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.POINTER(BaParams)]
 
 # name -> (restype, argtypes); mirrors include/lcm.h one to one (tests/test_abi.py checks the symbol list)
 _SIGNATURES = {
@@ -274,6 +307,18 @@ _SIGNATURES = {
     "lcm_pgo_linear_correct": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "lcm_pgo_close_loop": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(PoseResult), C.POINTER(PgoParams), _vp,
                                       C.POINTER(PgoInfo)]),
+    "lcm_ba_params_default": (None, [C.POINTER(BaParams)]),
+    "lcm_ba_error": (C.c_int, _BA_MAP + [C.POINTER(C.c_double), _vp]),
+    "lcm_ba_refine_cameras": (C.c_int, _BA_MAP + [_vp, _vp]),
+    "lcm_ba_refine_points": (C.c_int, _BA_MAP + [_vp, _vp]),
+    "lcm_ba_step_cameras": (C.c_int, _BA_MAP + [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "lcm_ba_step_points": (C.c_int, _BA_MAP + [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "lcm_ba_optimize": (C.c_int, _BA_MAP + [_vp, _vp, _vp, _vp, C.POINTER(BaInfo)]),
+    "lcm_ba_outliers": (C.c_int, _BA_MAP + [_vp, _vp, C.POINTER(C.c_double), _i32p]),
+    "lcm_ba_compact": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _i32p, _i32p]),
+    "lcm_ba_add_loop_observations": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int,
+                                                C.c_int, _i32p]),
+    "lcm_ba_refine_map": (C.c_int, _BA_MAP + [C.c_int, _vp, _vp, _vp, _vp, C.POINTER(BaMapReport)]),
     "lcm_query_scores": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _i32p]),
     "lcm_query_submit": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _i32p]),
     "lcm_query_collect": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i32p]),
@@ -523,6 +568,80 @@ def pgo_linear_correct(poses, past: int, curr: int, R_loop, valid=None) -> np.nd
     out = np.zeros(max(len(p), 1), PGO_POSE_DTYPE)
     _check(load_library().lcm_pgo_linear_correct(_ptr(p), _ptr(v), len(p), past, curr, _ptr(Rl), _ptr(out)))
     return out[:len(p)]
+
+
+_BA_FIELDS = ("fx", "fy", "cx", "cy", "eps", "damping", "min_update", "outlier_px", "min_spread", "spread_factor", "outer_iters",
+              "inner_iters", "min_cam_obs", "min_point_obs")
+
+
+def default_ba_params(**over) -> BaParams:
+    """lcm_ba_params_default (K zero, eps 1e-6, damping 1e-3, min_update 1e-6, outlier_px 5, min_spread 10, spread_factor 5,
+    outer_iters 5, inner_iters 5, min_cam_obs 10, min_point_obs 2) with any field given by name."""
+    p = BaParams()
+    load_library().lcm_ba_params_default(C.byref(p))
+    for k, v in over.items():
+        if k not in _BA_FIELDS:
+            raise TypeError(f"lcm_ba_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def ba_points(X) -> np.ndarray:
+    """BA_POINT_DTYPE[n] from coordinates [n, 3]."""
+    X = np.asarray(X, np.float64).reshape(-1, 3)
+    out = np.zeros(len(X), BA_POINT_DTYPE)
+    out["x"], out["y"], out["z"] = X[:, 0], X[:, 1], X[:, 2]
+    return out
+
+
+def ba_xyz(points) -> np.ndarray:
+    """float64[n, 3] from BA_POINT_DTYPE[n]."""
+    p = np.ascontiguousarray(points, BA_POINT_DTYPE)
+    return np.stack([p["x"], p["y"], p["z"]], 1) if len(p) else np.zeros((0, 3))
+
+
+def ba_obs(cam, point, uv) -> np.ndarray:
+    """BA_OBS_DTYPE[n] from camera indices [n], point indices [n] and pixels [n, 2]."""
+    cam = np.asarray(cam, np.int32)
+    out = np.zeros(len(cam), BA_OBS_DTYPE)
+    uv = np.asarray(uv, np.float64).reshape(len(cam), 2)
+    out["cam"], out["point"], out["u"], out["v"] = cam, np.asarray(point, np.int32), uv[:, 0], uv[:, 1]
+    return out
+
+
+def _ba_map(poses, valid, points, obs):
+    p, v = _pgo_graph(poses, valid)
+    return p, v, np.ascontiguousarray(points, BA_POINT_DTYPE), np.ascontiguousarray(obs, BA_OBS_DTYPE)
+
+
+def ba_compact(points, obs, flags):
+    """lcm_ba_compact (host only): (BA_POINT_DTYPE[kept], BA_OBS_DTYPE[kept observations], old_to_new int32[n])."""
+    x, o = np.ascontiguousarray(points, BA_POINT_DTYPE), np.ascontiguousarray(obs, BA_OBS_DTYPE)
+    f = np.ascontiguousarray(flags, np.uint8)
+    assert len(f) == len(x)
+    xo, oo, table = np.zeros(max(len(x), 1), BA_POINT_DTYPE), np.zeros(max(len(o), 1), BA_OBS_DTYPE), np.zeros(max(len(x), 1), np.int32)
+    np_, no = C.c_int32(0), C.c_int32(0)
+    _check(load_library().lcm_ba_compact(_ptr(x), len(x), _ptr(o), len(o), _ptr(f), _ptr(xo), len(x), _ptr(oo), len(o), _ptr(table),
+                                         C.byref(np_), C.byref(no)))
+    return xo[:np_.value], oo[:no.value], table[:len(x)]
+
+
+def ba_add_loop_observations(matches, mask, past_table, curr_table, curr_kp, curr: int, n_points: int, obs):
+    """lcm_ba_add_loop_observations (host only): the observation list with the loop's new observations appended (BA_OBS_DTYPE) and
+    their number; curr_table (int32[n_curr_kp], C-contiguous) is updated in place."""
+    m = np.ascontiguousarray(matches, DMATCH_DTYPE)
+    k = np.ascontiguousarray(mask, np.uint8)
+    assert len(k) == len(m) and curr_table.dtype == np.int32 and curr_table.flags["C_CONTIGUOUS"]
+    past = np.ascontiguousarray(past_table, np.int32)
+    kp = np.ascontiguousarray(curr_kp, np.float32).reshape(-1, 2)
+    assert len(kp) == len(curr_table)
+    o = np.ascontiguousarray(obs, BA_OBS_DTYPE)
+    out = np.zeros(len(o) + int(np.count_nonzero(k)) + 1, BA_OBS_DTYPE)
+    out[:len(o)] = o
+    n = C.c_int32(0)
+    _check(load_library().lcm_ba_add_loop_observations(_ptr(m), _ptr(k), len(m), _ptr(past), len(past), _ptr(curr_table), _ptr(kp), len(kp),
+                                                       curr, n_points, _ptr(out), len(o), len(out), C.byref(n)))
+    return out[:len(o) + n.value], n.value
 
 
 def _point_pairs(pts) -> np.ndarray:
@@ -1294,6 +1413,78 @@ class Matcher:
         info = PgoInfo()
         _check(self._lib.lcm_pgo_close_loop(self._h, _ptr(p), _ptr(v), len(p), past, curr, C.byref(pr), _ref(pp), _ptr(out), C.byref(info)))
         return out[:len(p)], info
+
+    # -- after the loop: alternating bundle adjustment and outlier removal (lcm_ba_*) --
+    def ba_error(self, poses, points, obs, bp: BaParams, valid=None, per_observation: bool = False):
+        """computeReprojectionError: the mean, or (mean, float64[n_obs]) with per_observation."""
+        p, v, x, o = _ba_map(poses, valid, points, obs)
+        mean, each = C.c_double(-1.0), (np.zeros(max(len(o), 1)) if per_observation else None)
+        _check(self._lib.lcm_ba_error(self._h, _ptr(p), _ptr(v), len(p), _ptr(x), len(x), _ptr(o), len(o), _ref(bp), C.byref(mean), _ptr(each)))
+        return (mean.value, each[:len(o)]) if per_observation else mean.value
+
+    def ba_refine_cameras(self, poses, points, obs, bp: BaParams, valid=None):
+        """The camera phase: (PGO_POSE_DTYPE[n_poses], BA_ELEM_INFO_DTYPE[n_poses])."""
+        p, v, x, o = _ba_map(poses, valid, points, obs)
+        out, info = np.zeros(max(len(p), 1), PGO_POSE_DTYPE), np.zeros(max(len(p), 1), BA_ELEM_INFO_DTYPE)
+        _check(self._lib.lcm_ba_refine_cameras(self._h, _ptr(p), _ptr(v), len(p), _ptr(x), len(x), _ptr(o), len(o), _ref(bp), _ptr(out), _ptr(info)))
+        return out[:len(p)], info[:len(p)]
+
+    def ba_refine_points(self, poses, points, obs, bp: BaParams, valid=None):
+        """The point phase: (BA_POINT_DTYPE[n_points], BA_ELEM_INFO_DTYPE[n_points])."""
+        p, v, x, o = _ba_map(poses, valid, points, obs)
+        out, info = np.zeros(max(len(x), 1), BA_POINT_DTYPE), np.zeros(max(len(x), 1), BA_ELEM_INFO_DTYPE)
+        _check(self._lib.lcm_ba_refine_points(self._h, _ptr(p), _ptr(v), len(p), _ptr(x), len(x), _ptr(o), len(o), _ref(bp), _ptr(out), _ptr(info)))
+        return out[:len(x)], info[:len(x)]
+
+    def _ba_step(self, call, width, n_elem, p, v, x, o, bp):
+        n = max(n_elem, 1)
+        r, J = np.zeros((max(len(o), 1), 2)), np.zeros((max(len(o), 1), 2, width))
+        H, g, dp, info = np.zeros((n, width, width)), np.zeros((n, width)), np.zeros((n, width)), np.zeros(n, BA_ELEM_INFO_DTYPE)
+        _check(call(self._h, _ptr(p), _ptr(v), len(p), _ptr(x), len(x), _ptr(o), len(o), _ref(bp), _ptr(r), _ptr(J), _ptr(H), _ptr(g), _ptr(dp),
+                    _ptr(info)))
+        return r[:len(o)], J[:len(o)], H[:n_elem], g[:n_elem], dp[:n_elem], info[:n_elem]
+
+    def ba_step_cameras(self, poses, points, obs, bp: BaParams, valid=None):
+        """The test seam, one linearisation of every camera: (r float64[n_obs, 2], J float64[n_obs, 2, 6], H float64[n_poses, 6, 6]
+        before damping, g and dp float64[n_poses, 6], BA_ELEM_INFO_DTYPE[n_poses])."""
+        p, v, x, o = _ba_map(poses, valid, points, obs)
+        return self._ba_step(self._lib.lcm_ba_step_cameras, 6, len(p), p, v, x, o, bp)
+
+    def ba_step_points(self, poses, points, obs, bp: BaParams, valid=None):
+        """The test seam, one linearisation of every point: (r float64[n_obs, 2], J float64[n_obs, 2, 3], H float64[n_points, 3, 3]
+        before damping, g and dp float64[n_points, 3], BA_ELEM_INFO_DTYPE[n_points])."""
+        p, v, x, o = _ba_map(poses, valid, points, obs)
+        return self._ba_step(self._lib.lcm_ba_step_points, 3, len(x), p, v, x, o, bp)
+
+    def ba_optimize(self, poses, points, obs, bp: BaParams, valid=None):
+        """alternatingBundleAdjustment: (PGO_POSE_DTYPE[n_poses], BA_POINT_DTYPE[n_points], BA_ELEM_INFO_DTYPE[n_poses],
+        BA_ELEM_INFO_DTYPE[n_points], BaInfo)."""
+        p, v, x, o = _ba_map(poses, valid, points, obs)
+        po, xo = np.zeros(max(len(p), 1), PGO_POSE_DTYPE), np.zeros(max(len(x), 1), BA_POINT_DTYPE)
+        ci, xi = np.zeros(max(len(p), 1), BA_ELEM_INFO_DTYPE), np.zeros(max(len(x), 1), BA_ELEM_INFO_DTYPE)
+        info = BaInfo()
+        _check(self._lib.lcm_ba_optimize(self._h, _ptr(p), _ptr(v), len(p), _ptr(x), len(x), _ptr(o), len(o), _ref(bp), _ptr(po), _ptr(xo),
+                                         _ptr(ci), _ptr(xi), C.byref(info)))
+        return po[:len(p)], xo[:len(x)], ci[:len(p)], xi[:len(x)], info
+
+    def ba_outliers(self, poses, points, obs, bp: BaParams, valid=None):
+        """The outlier flags: (flags uint8[n_points], max_err float64[n_points], threshold, count)."""
+        p, v, x, o = _ba_map(poses, valid, points, obs)
+        flags, worst = np.zeros(max(len(x), 1), np.uint8), np.zeros(max(len(x), 1))
+        thr, n = C.c_double(-1.0), C.c_int32(-1)
+        _check(self._lib.lcm_ba_outliers(self._h, _ptr(p), _ptr(v), len(p), _ptr(x), len(x), _ptr(o), len(o), _ref(bp), _ptr(flags), _ptr(worst),
+                                         C.byref(thr), C.byref(n)))
+        return flags[:len(x)], worst[:len(x)], thr.value, n.value
+
+    def ba_refine_map(self, poses, points, obs, bp: BaParams, valid=None, second_outer_iters: int = 0):
+        """src/main.cpp:1543-1669 in one call: (PGO_POSE_DTYPE[n_poses], BA_POINT_DTYPE[kept], BA_OBS_DTYPE[kept observations],
+        old_to_new int32[n_points], BaMapReport)."""
+        p, v, x, o = _ba_map(poses, valid, points, obs)
+        po, xo, oo = np.zeros(max(len(p), 1), PGO_POSE_DTYPE), np.zeros(max(len(x), 1), BA_POINT_DTYPE), np.zeros(max(len(o), 1), BA_OBS_DTYPE)
+        table, rep = np.zeros(max(len(x), 1), np.int32), BaMapReport()
+        _check(self._lib.lcm_ba_refine_map(self._h, _ptr(p), _ptr(v), len(p), _ptr(x), len(x), _ptr(o), len(o), _ref(bp), second_outer_iters,
+                                           _ptr(po), _ptr(xo), _ptr(oo), _ptr(table), C.byref(rep)))
+        return po[:len(p)], xo[:rep.n_points], oo[:rep.n_obs], table[:len(x)], rep
 
     # -- loop search -------------------------------------------------------------------------------
     def query_scores(self, query, query_frame_id: int) -> Tuple[np.ndarray, np.ndarray]:

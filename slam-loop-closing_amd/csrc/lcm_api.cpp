@@ -232,6 +232,7 @@ void lcm_destroy(lcm_handle* h) {
     (void)hipFree(h->epi.d_best); (void)hipFree(h->epi.d_counts); (void)hipFree(h->epi.d_res); (void)hipFree(h->epi.d_mask);
     (void)hipFree(h->pose.d_E); (void)hipFree(h->pose.d_mask_in); (void)hipFree(h->pose.d_cand); (void)hipFree(h->pose.d_res); (void)hipFree(h->pose.d_mask);
     (void)hipFree(h->pgo.d_in); (void)hipFree(h->pgo.d_work);
+    (void)hipFree(h->ba.d_map);
     (void)hipFree(h->lo.d_seeds); (void)hipFree(h->lo.d_info); (void)hipFree(h->lo.d_models); (void)hipFree(h->lo.d_seam);
     for (QuerySlot& q : h->qslots) {
         (void)hipFree(q.d_query); (void)hipFree(q.d_scores); (void)hipFree(q.d_dist); (void)hipFree(q.d_meta);

@@ -12,6 +12,7 @@
 //   lcm_pose.cpp       relative pose of the verified candidates and the best loop (lcm_pose_*)
 //   lcm_lo.cpp         local optimisation of the RANSAC's best hypotheses (lcm_lo_*)
 //   lcm_pgo.cpp        pose-graph Gauss-Newton correction of the closed loop (lcm_pgo_*)
+//   lcm_ba.cpp         alternating bundle adjustment and outlier removal after the loop (lcm_ba_*)
 //   lcm_verify.cpp     the three as one staged pipeline over a VerifyPlan (lcm_verify_host.h); the store's and the host-list forms
 // Not installed; the public surface is include/lcm.h.
 #pragma once
@@ -305,6 +306,11 @@ struct lcm_handle {
         uint8_t* d_in = nullptr;      size_t d_in_n = 0;
         double* d_work = nullptr;     size_t d_work_n = 0;
     } pgo;
+    // bundle adjustment (lcm_ba.cpp): one map's [poses | points | observations | tables | valid] and everything the kernels write
+    // behind it (element infos, mean errors, partial sums, flags, the step calls' seam) as bytes
+    struct BaScratch {
+        uint8_t* d_map = nullptr;     size_t d_map_n = 0;
+    } ba;
     lcm_launch_info info{};
     bool info_pending = false;
 };

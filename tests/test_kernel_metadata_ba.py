@@ -1,0 +1,104 @@
+"""Code-object metadata of the bundle adjustment (lcm_ba.hip; hipcc cross-compiles gfx950 without a GPU): exactly the kernels the
+file's header names, without scratch memory or spills, each within the VGPR and LDS budget the header states; and from the source
+text: the projection, the residual, the column, the running sums and the 3 x 3 Cholesky defined once in lcm_ba_device.h, the
+rotation's exp / log and the 6 x 6 Cholesky taken from the pose graph's header and not restated, all called from the kernels, and no
+atomic.  Metadata fields and source structure only."""
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "slam-loop-closing_amd", "csrc")
+HIPCC = "/opt/rocm/bin/hipcc"
+FIELDS = ("private_segment_fixed_size", "vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "group_segment_fixed_size")
+# kernel -> (VGPRs, LDS bytes), the file header's budget.  A camera's workgroup may use what two workgroups per compute unit leave
+# each other (256 VGPRs at one wave per SIMD and workgroup, 61488 of 160 KiB of LDS)
+BUDGET = {"k_ba_cameras": (256, 61488), "k_ba_points": (160, 0), "k_ba_outliers": (64, 0), "k_ba_error": (64, 2176), "k_ba_mean": (64, 2176)}
+
+
+def kernels_of(src):
+    return re.findall(r"__global__[^\n]*\bvoid\s+(\w+)\s*\(", src)
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+def test_kernels_use_no_scratch_and_fit_their_budgets(tmp_path):
+    out = tmp_path / "lcm_ba.s"
+    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-x", "hip",
+                           os.path.join(CSRC, "lcm_ba.hip"), "-o", str(out)], stderr=subprocess.DEVNULL)
+    text = out.read_text()
+    meta = text[text.index("amdhsa.kernels:"):]
+    ks = {}
+    for block in re.split(r"\n  - \.a", meta)[1:]:
+        name = re.search(r"\.name:\s+(\S+)", block).group(1)
+        short = re.search(r"(k_ba_[a-z]+)E", name).group(1)
+        ks[short] = {k: int(re.search(rf"\.{k}:\s+(\d+)", block).group(1)) for k in FIELDS}
+    assert sorted(ks) == sorted(BUDGET)
+    for name, m in sorted(ks.items()):
+        print(name, m)
+        vgprs, lds = BUDGET[name]
+        assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0, (name, m)
+        assert m["vgpr_count"] <= vgprs and m["group_segment_fixed_size"] <= lds, (name, m)
+        assert (m["group_segment_fixed_size"] > 0) == (lds > 0), (name, m)
+
+
+def test_the_header_names_every_kernel_and_states_the_budget_and_the_order():
+    src = open(os.path.join(CSRC, "lcm_ba.hip")).read()
+    head = src[: src.index("#include")]
+    assert sorted(kernels_of(src)) == sorted(BUDGET)
+    for name in BUDGET:
+        assert re.search(rf"^// {name}\s", head, flags=re.M), name
+    flat = re.sub(r"\s+", " ", head.replace("\n//", " "))
+    budget = flat[flat.index("Budget"):]
+    assert "no scratch, no spills" in budget
+    for names, (vgprs, lds) in ((("k_ba_cameras",), (256, 61488)), (("k_ba_points",), (160, 0)), (("k_ba_outliers",), (64, 0)),
+                                (("k_ba_error", "k_ba_mean"), (64, 2176))):
+        what = f"at most {vgprs} VGPRs and " + (f"{lds} bytes of LDS" if lds else "no LDS")
+        listed = " and ".join(names)
+        assert re.search(rf"{listed} {re.escape(what)}", budget), (listed, what)
+        assert all(BUDGET[n] == (vgprs, lds) for n in names)
+    # the order of the sums is fixed and stated
+    assert "Summation order over a camera's observations" in flat and "added left to right" in flat and "Summation order: one running sum per entry in table order" in flat
+    make = open(os.path.join(CSRC, "Makefile")).read()
+    assert "lcm_ba.hip" in make and "lcm_ba.cpp" in make and "lcm_ba_device.h" in make and "lcm_ba_host.h" in make
+
+
+def test_the_arithmetic_exists_once_and_is_called_from_the_kernels():
+    src = open(os.path.join(CSRC, "lcm_ba.hip")).read()
+    dev = open(os.path.join(CSRC, "lcm_ba_device.h")).read()
+    pgo = open(os.path.join(CSRC, "lcm_pgo_device.h")).read()
+    for fn in ("void ba_camera_point(", "void ba_residual(", "double ba_error(", "void ba_column(", "bool ba_chol3(", "void ba_lower_solve3(",
+               "void ba_upper_solve3(", "bool ba_solve6(", "bool ba_solve3(", "void ba_accumulate("):
+        assert dev.count(fn) == 1 and fn not in src, fn
+    # the pose graph's functions are used, not restated: defined there once, nowhere else
+    for fn in ("void pgo_exp(", "bool pgo_log(", "void pgo_apply(", "bool pgo_chol6(", "void pgo_lower_solve6(", "void pgo_upper_solve6("):
+        assert pgo.count(fn) == 1 and fn not in dev and fn not in src, fn
+    assert '#include "lcm_pgo_device.h"' in dev and "lcm_pgo" not in src and re.findall(r'#include "([^"]+)"', src) == ["lcm_ba_device.h"]
+    dev_code = re.sub(r"//[^\n]*", "", dev)
+    code = re.sub(r"//[^\n]*", "", src)                     # the kernels' text without its comments
+    assert dev_code.count("pgo_chol6(") == 1 and dev_code.count("pgo_lower_solve6(") == 1 and dev_code.count("pgo_upper_solve6(") == 1
+    assert code.count("pgo_exp(") == 2 and code.count("pgo_log(") == 1          # the thirteen vectors' rotations and the write-back; the start
+    assert code.count("ba_solve6(") == 1 and code.count("ba_solve3(") == 1 and code.count("ba_accumulate<") == 2
+    assert code.count("ba_residual(") >= 6 and code.count("ba_column(") == 3 and len(re.findall(r"\bba_error\(", code)) == 2
+    words = set(re.findall(r"\b\w+\b", code))
+    assert not words & {"atan2", "sin", "cos", "acos", "asin", "sincos", "theta"}
+    assert not (set(re.findall(r"\b\w+\b", dev_code)) & {"atan2", "sin", "cos", "acos", "asin", "sincos"})
+    # no floating-point atomics: no atomic at all
+    assert not re.search(r"atomic", code, flags=re.I) and not re.search(r"atomic", dev_code, flags=re.I)
+    assert "asm" not in words
+    # the host runs none of it but through lcm_ba_host.h
+    host = re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, "lcm_ba.cpp")).read())
+    for fn in ("pgo_exp(", "pgo_log(", "ba_residual(", "ba_chol3(", "ba_solve6("):
+        assert fn not in host, fn
+    assert "#pragma clang fp contract(off)" in dev and "fp contract(off)" in src
+
+
+def test_kernel_names_are_the_files_own():
+    every = []
+    for f in sorted(os.listdir(CSRC)):
+        if f.endswith(".hip"):
+            ks = kernels_of(open(os.path.join(CSRC, f)).read())
+            every += ks
+            assert all(k.startswith("k_ba_") == (f == "lcm_ba.hip") for k in ks), f
+    assert len(every) == len(set(every)) and not any("pgo" in k for k in every if k.startswith("k_ba_"))
