@@ -896,6 +896,131 @@ LCM_API int  lcm_ba_refine_map(lcm_handle* h, const lcm_pgo_pose* poses, const u
                                lcm_pgo_pose* poses_out, lcm_ba_point* points_out, lcm_ba_obs* obs_out, int32_t* old_to_new,
                                lcm_ba_map_report* report);
 
+/* ---- before the loop: the map (keyframe gates, triangulation, filters, merge) on the device -------------------------------- */
+/* src/main.cpp:1152-1351: what builds the 3-D points, the observation list and the keypoint -> point tables that the calls above
+ * take.  A pair is (view 1 = the last keyframe = the match's query side, view 2 = the new keyframe = the train side) with
+ * world-to-camera poses P1, P2 (lcm_pgo_pose) and records lcm_point_pair {qx, qy, tx, ty}, one mask byte each.  The loop over
+ * the matches (:1261-1341) is a filter per record, an ordered compaction and a last-writer scatter: a knnMatch list holds every
+ * query_idx once, so a record's table look-up depends on no earlier record and its new point index is the number of new points
+ * before it (lcm_map_device.h, lcm_map.hip).  In double, every product and sum rounded on its own (no contraction
+ * into fused multiply-adds), row sums left to right:
+ *   per pair      on the host (lcm_map_host.h), returned in lcm_map_pair_info: C_i = -(R_i^T t_i);
+ *                 baseline = sqrt(sum of squares of C2 - C1); the 3 x 4 matrices K [R_i | t_i], row 0 = fx row0 + cx row2,
+ *                 row 1 = fy row1 + cy row2, row 2 = row2 of [R_i | t_i]; cos_min = cos(min_parallax_deg * pi / 180)
+ *   mask          mask byte 0: LCM_MAP_NOT_INLIER (mask == NULL: every record takes part)
+ *   triangulation cv::triangulatePoints' system: the rows of A are x1 P1[2] - P1[0], y1 P1[2] - P1[1], x2 P2[2] - P2[0],
+ *                 y2 P2[2] - P2[1] with the coordinates the floats converted to double; M = A^T A, its ten sums over the four rows
+ *                 in that order; the homogeneous point is the eigenvector of M's smallest eigenvalue by a cyclic Jacobi over the
+ *                 six pairs (p, q) in lexicographic order with a fixed number of sweeps (the local optimisation's rotation
+ *                 formulae), the column of the smallest diagonal entry, first of equals.  Stated departures from OpenCV: there
+ *                 is no SVD, and the vector is not rounded to float (OpenCV returns CV_32F, which :1268-1273 reads)
+ *   point         |w| < 1e-9: LCM_MAP_NO_POINT (:1269); otherwise X = (x / w, y / w, z / w)
+ *   depth         depth_i = (R_i X + t_i).z; depth1 <= 0 || depth2 <= 0: LCM_MAP_REJ_DEPTH; rel = depth1 / baseline,
+ *                 rel < min_depth || rel > max_depth: LCM_MAP_REJ_DEPTH.  IEEE decides at baseline == 0, as in the reference
+ *   parallax      (:200-222) the rays X - C_i and their norms; a norm < 1e-9 is parallax 0 and rejected (cos_parallax = 1);
+ *                 otherwise c = the dot product of the two normalised rays clamped to [-1, 1]; c > cos_min:
+ *                 LCM_MAP_REJ_PARALLAX.  Stated departure: the cosine is compared and there is no acos, so a record whose angle
+ *                 lies within rounding of the threshold may fall on the other side
+ *   reprojection  (:227-246) err_i as computeSingleReprojError, 1e9 at z <= 0; err1 > max_reproj || err2 > max_reproj:
+ *                 LCM_MAP_REJ_REPROJ; otherwise LCM_MAP_ACCEPTED
+ * Each record gives one status byte and one lcm_map_tri; every field of it is computed for every record that has a point,
+ * rejected or not, and all are zero for LCM_MAP_NOT_INLIER and LCM_MAP_NO_POINT.  The same call gives the same bytes.
+ * Limits: LCM_MAP_MAX_PAIRS pairs and LCM_MAP_MAX_RECORDS records per call, LCM_ERR_CAPACITY above them, decided from the counts
+ * before any buffer is read.  Ordered on the handle's stream and finished on return; lcm_last_launch_info: kernel_ms, launches,
+ * pairs = records. */
+#define LCM_MAP_MAX_PAIRS 4096
+#define LCM_MAP_MAX_RECORDS 16777216
+typedef enum lcm_map_status { LCM_MAP_NOT_INLIER = 0, LCM_MAP_NO_POINT = 1, LCM_MAP_REJ_DEPTH = 2, LCM_MAP_REJ_PARALLAX = 3,
+                              LCM_MAP_REJ_REPROJ = 4, LCM_MAP_ACCEPTED = 5, LCM_MAP_MERGED = 6, LCM_MAP_NEW = 7 } lcm_map_status;
+typedef enum lcm_map_verdict { LCM_MAP_KEYFRAME = 0, LCM_MAP_FEW_MATCHES = 1, LCM_MAP_LITTLE_MOTION = 2, LCM_MAP_MUCH_MOTION = 3,
+                               LCM_MAP_NO_POSE = 4, LCM_MAP_FEW_INLIERS = 5 } lcm_map_verdict;
+typedef struct lcm_map_params {       /* defaults = the reference's constants (:38-48) */
+    double fx, fy, cx, cy;            /* the camera matrix K; the defaults leave it zero: fx <= 0 or fy <= 0 is LCM_ERR_INVALID_ARG */
+    double min_parallax_deg;          /* 1.0, finite, in [0, 180] */
+    double max_reproj;                /* 4.0 px, >= 0 */
+    double min_depth, max_depth;      /* 0.1, 50.0: in units of the baseline */
+    double min_displacement;          /* 20.0 px: below it LCM_MAP_LITTLE_MOTION */
+    double max_displacement;          /* 150.0 px: above it LCM_MAP_MUCH_MOTION */
+    double min_inlier_ratio;          /* 0.3 */
+    int32_t min_tracked;              /* 100: fewer matches is LCM_MAP_FEW_MATCHES */
+    int32_t min_inliers;              /* 50 */
+    int32_t min_pose_inliers;         /* 10: estimateRelativePoseFromEssential's (:611) */
+    int32_t reserved[3];              /* ignored */
+} lcm_map_params;                     /* 112 bytes */
+typedef struct lcm_map_tri { double X[3]; double depth1, depth2, cos_parallax, err1, err2; } lcm_map_tri;       /* 64 bytes */
+typedef struct lcm_map_pair_info {
+    double baseline, cos_min;         /* what the host planner computed for the pair */
+    int32_t counts[8];                /* records per lcm_map_status (LCM_MAP_MERGED and LCM_MAP_NEW: 0 here) */
+} lcm_map_pair_info;                  /* 48 bytes */
+typedef struct lcm_map_keyframe_report {
+    lcm_pgo_pose pose;                /* the new keyframe's pose (:1217-1218); zero unless the verdict is LCM_MAP_KEYFRAME */
+    double median, baseline;          /* computeMedianDisplacement; the pair's baseline */
+    int32_t verdict;                  /* lcm_map_verdict */
+    int32_t n_matches, n_inliers;     /* the list's length; countNonZero(inlierMask) (:1191) */
+    int32_t n_new, n_merged;          /* points created; observations added to existing points */
+    int32_t reserved;
+    int32_t counts[8];                /* records per lcm_map_status after the merge */
+} lcm_map_keyframe_report;            /* 168 bytes */
+LCM_API void lcm_map_params_default(lcm_map_params* p);
+/* computeMedianDisplacement (:171-189) per pair, lcm_epi_verify_pairs's layout: dx = (double)(tx - qx) with the subtraction in
+ * float as the reference's is, dy likewise, d = sqrt(dx dx + dy dy); median[p] = the element at index n / 2 of the sorted
+ * values, 0.0 for an empty pair.  An exact selection (a radix select over the 64-bit patterns, one workgroup per pair), bit for
+ * bit what sorting gives.  The coordinates must be finite. */
+LCM_API int  lcm_map_median_displacement(lcm_handle* h, const lcm_point_pair* pts, const size_t* offsets, int n_pairs, double* median);
+/* The arithmetic above for many pairs in one launch, one lane per record.  Pair p owns pts[offsets[p] .. offsets[p + 1]), the
+ * poses poses1[p] and poses2[p] and info[p]; mask (may be NULL), tri and status: offsets[n_pairs] records.  mp is required (K
+ * has no default).  Refused with LCM_ERR_INVALID_ARG before anything is launched or written: a NULL buffer, a bad mp field, a
+ * non-finite double in a pose, a pose R with max |R R^T - I| > 1e-6 or a negative determinant, offsets that decrease. */
+LCM_API int  lcm_map_triangulate_pairs(lcm_handle* h, const lcm_point_pair* pts, const size_t* offsets, int n_pairs, const uint8_t* mask,
+                                       const lcm_pgo_pose* poses1, const lcm_pgo_pose* poses2, const lcm_map_params* mp,
+                                       lcm_map_tri* tri, uint8_t* status, lcm_map_pair_info* info);
+/* :1315-1340 for one pair, on the device.  matches, tri, status: n records (status as lcm_map_triangulate_pairs wrote it);
+ * table1 (n_kp1 entries) and table2 (n_kp2): the keypoint -> point tables of keyframes kf1 and kf2, -1 = none, updated in place;
+ * n_points: the map's points so far.  For every LCM_MAP_ACCEPTED record in list order: if table1[query_idx] != -1 one observation
+ * {kf2, that point, (double)tx, (double)ty} is appended and its status becomes LCM_MAP_MERGED; otherwise point n_points + (new
+ * points before it) is appended with tri's X, two observations {kf1, idx, q} and {kf2, idx, t} are appended,
+ * table1[query_idx] = idx and the status becomes LCM_MAP_NEW; table2[train_idx] = the point in both cases, and where several
+ * accepted records share a train_idx the last in list order wins.  points_out receives the *n_new new points (byte for byte tri's
+ * X), obs_out the 2 *n_new + *n_merged new observations, status_out (n bytes) every record's status.  pts: the records' pixels.
+ * Refused on the host in O(n) before anything is launched or written (LCM_ERR_INVALID_ARG): a list with a repeated query_idx
+ * among all its records (the reference's sequential meaning differs there, and a knnMatch list has none), an index outside its
+ * table, a table entry outside [-1, n_points), a status byte above LCM_MAP_ACCEPTED.  Too small a cap_points or cap_obs:
+ * LCM_ERR_CAPACITY with the needed counts in *n_new and *n_merged and nothing else written. */
+LCM_API int  lcm_map_merge(lcm_handle* h, const lcm_dmatch* matches, const lcm_point_pair* pts, const lcm_map_tri* tri, const uint8_t* status,
+                           int n, int kf1, int kf2, int32_t* table1, int n_kp1, int32_t* table2, int n_kp2, int n_points,
+                           lcm_ba_point* points_out, int cap_points, lcm_ba_obs* obs_out, int cap_obs, uint8_t* status_out, int* n_new,
+                           int* n_merged);
+/* One iteration of :1152-1351 on host lists: matches and pts (n_matches records, query = the last keyframe kf_last with pose
+ * pose_last and table table_last, train = the frame that may become keyframe kf_new, whose table table_new the caller has filled
+ * with -1).  In order: n_matches < min_tracked: LCM_MAP_FEW_MATCHES (:1156); the median gates: LCM_MAP_LITTLE_MOTION /
+ * LCM_MAP_MUCH_MOTION (:1170, :1176); estimateRelativePoseFromEssential = lcm_epi_verify_pairs followed by
+ * lcm_pose_recover_pairs, with lp != NULL lcm_lo_verify_pairs in between: fewer than 8 records, LCM_POSE_NO_MODEL or
+ * n_good < min_pose_inliers: LCM_MAP_NO_POSE; the inlier mask is the pose's mask_out (:601-609); n_inliers < min_inliers or
+ * n_inliers / n_matches < min_inlier_ratio: LCM_MAP_FEW_INLIERS (:1194); R_new = R R_last, t_new = R t_last + t (:1217-1218);
+ * lcm_map_triangulate_pairs and lcm_map_merge.  Every verdict but LCM_MAP_KEYFRAME leaves the tables and the output buffers
+ * untouched; the refusals are lcm_map_merge's and the stages', and LCM_ERR_CAPACITY leaves them untouched too (report->n_new and
+ * n_merged then hold the needed counts).  status_out (n_matches bytes) may be NULL.  The stages are enqueued on the handle's
+ * stream; only the small verdict values (the median, the pose record, the counts) come back between them.  ep: the RANSAC's
+ * parameters with the same K; pp may be NULL. */
+LCM_API int  lcm_map_add_keyframe(lcm_handle* h, const lcm_dmatch* matches, const lcm_point_pair* pts, int n_matches, int kf_last,
+                                  const lcm_pgo_pose* pose_last, int32_t* table_last, int n_kp_last, int kf_new, int32_t* table_new,
+                                  int n_kp_new, int n_points, const lcm_map_params* mp, const lcm_epi_params* ep,
+                                  const lcm_lo_params* lp, const lcm_pose_params* pp, lcm_ba_point* points_out, int cap_points,
+                                  lcm_ba_obs* obs_out, int cap_obs, uint8_t* status_out, lcm_map_keyframe_report* report);
+/* The same with the matching included, on the SIFT keyframe store: lcm_pose_db_verify_pairs (lp != NULL: lcm_lo_db_verify_pairs)
+ * on the stored pair {last_slot, curr_slot} (matchFeatures(desc[last], currDesc) at :1154 makes the last keyframe the query; its
+ * default ratio is 0.75), then the map stages on the records, the matrix and the mask that call left on the device, before the
+ * lists are copied back.  The keypoint counts are the slots' rows.  result, info (lp != NULL), pose_result: one record each; out,
+ * pts, mask, pose_mask (`cap` records; the masks may be NULL) and offsets (2 entries) come back exactly as that call returns them;
+ * the map's arguments and *report exactly as lcm_map_add_keyframe's on those lists.  A frame that is not accepted is removed by the
+ * caller with lcm_l2_db_truncate.  `cap` too small: as lcm_pose_db_verify_pairs, and nothing of the map is written either. */
+LCM_API int  lcm_map_db_track(lcm_handle* h, int last_slot, int curr_slot, double ratio, const lcm_epi_params* ep, const lcm_lo_params* lp,
+                              const lcm_pose_params* pp, lcm_epi_result* result, lcm_lo_info* info, lcm_pose_result* pose_result,
+                              lcm_dmatch* out, lcm_point_pair* pts, uint8_t* mask, uint8_t* pose_mask, size_t cap, size_t* offsets,
+                              int kf_last, const lcm_pgo_pose* pose_last, int32_t* table_last, int kf_new, int32_t* table_new,
+                              int n_points, const lcm_map_params* mp, lcm_ba_point* points_out, int cap_points, lcm_ba_obs* obs_out,
+                              int cap_obs, uint8_t* status_out, lcm_map_keyframe_report* report);
+
 /* ---- loop search against the stored database --------------------------------------------------------- */
 /* Score `query` (id query_frame_id) against every stored frame with query_frame_id - id >= min_gap, ascending
  * slot order.  out_scores / out_frame_ids need room for lcm_db_size() records. */

@@ -134,6 +134,29 @@ BA_CONVERGED, BA_MAX_ITERS, BA_SOLVE_FAILED, BA_HALF_TURN, BA_SKIPPED = 0, 1, 2,
 BA_MAX_CAMERAS, BA_MAX_POINTS, BA_MAX_OBS, BA_MAX_ITERS_PER_LOOP = 4096, 1 << 24, 1 << 24, 16
 
 
+class MapParams(C.Structure):
+    """lcm_map_params: the camera matrix, the triangulation's filters and the keyframe gates (112 bytes)."""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("min_parallax_deg", C.c_double),
+                ("max_reproj", C.c_double), ("min_depth", C.c_double), ("max_depth", C.c_double), ("min_displacement", C.c_double),
+                ("max_displacement", C.c_double), ("min_inlier_ratio", C.c_double), ("min_tracked", C.c_int32), ("min_inliers", C.c_int32),
+                ("min_pose_inliers", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class MapKeyframeReport(C.Structure):
+    """lcm_map_keyframe_report: the new keyframe's pose (R row-major, t), the median displacement, the baseline, the verdict, the
+    list's length, the pose's inliers, the points created and merged, the records per status (168 bytes)."""
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("median", C.c_double), ("baseline", C.c_double), ("verdict", C.c_int32),
+                ("n_matches", C.c_int32), ("n_inliers", C.c_int32), ("n_new", C.c_int32), ("n_merged", C.c_int32), ("reserved", C.c_int32),
+                ("counts", C.c_int32 * 8)]
+
+
+# lcm_map_status, lcm_map_verdict
+MAP_NOT_INLIER, MAP_NO_POINT, MAP_REJ_DEPTH, MAP_REJ_PARALLAX, MAP_REJ_REPROJ, MAP_ACCEPTED, MAP_MERGED, MAP_NEW = range(8)
+MAP_KEYFRAME, MAP_FEW_MATCHES, MAP_LITTLE_MOTION, MAP_MUCH_MOTION, MAP_NO_POSE, MAP_FEW_INLIERS = range(6)
+MAP_MAX_PAIRS, MAP_MAX_RECORDS = 4096, 1 << 24
+_MAP_FIELDS = tuple(f[0] for f in MapParams._fields_[:-1])
+
+
 class LoParams(C.Structure):
     """lcm_lo_params: the rounds of the RANSAC's local optimisation and their threshold multipliers (96 bytes)."""
     _fields_ = [("rounds", C.c_int32), ("seeds", C.c_int32), ("mult", C.c_double * 8), ("reserved", C.c_uint32 * 6)]
@@ -197,6 +220,10 @@ BA_OBS_DTYPE = np.dtype([("cam", "<i4"), ("point", "<i4"), ("u", "<f8"), ("v", "
 BA_ELEM_INFO_DTYPE = np.dtype([("last_update", "<f8"), ("cost", "<f8"), ("iterations", "<i4"), ("status", "<i4")])    # lcm_ba_elem_info
 assert BA_POINT_DTYPE.itemsize == 24 and BA_OBS_DTYPE.itemsize == 24 and BA_ELEM_INFO_DTYPE.itemsize == 24
 assert C.sizeof(BaParams) == 112 and C.sizeof(BaInfo) == 184 and C.sizeof(BaMapReport) == 56
+MAP_TRI_DTYPE = np.dtype([("X", "<f8", (3,)), ("depth1", "<f8"), ("depth2", "<f8"), ("cos_parallax", "<f8"), ("err1", "<f8"),
+                          ("err2", "<f8")])                                    # lcm_map_tri
+MAP_PAIR_INFO_DTYPE = np.dtype([("baseline", "<f8"), ("cos_min", "<f8"), ("counts", "<i4", (8,))])      # lcm_map_pair_info
+assert MAP_TRI_DTYPE.itemsize == 64 and MAP_PAIR_INFO_DTYPE.itemsize == 48 and C.sizeof(MapParams) == 112 and C.sizeof(MapKeyframeReport) == 168
 LO_INFO_DTYPE = np.dtype([("seed_iter", "<i4"), ("round", "<i4"), ("n_inliers_ransac", "<i4"), ("status", "<i4")])    # lcm_lo_info
 assert LO_INFO_DTYPE.itemsize == C.sizeof(LoInfo) == 16 and C.sizeof(LoParams) == 96
 assert SCORE_DTYPE.itemsize == C.sizeof(Score) == 8
@@ -319,6 +346,17 @@ _SIGNATURES = {
     "lcm_ba_add_loop_observations": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int,
                                                 C.c_int, _i32p]),
     "lcm_ba_refine_map": (C.c_int, _BA_MAP + [C.c_int, _vp, _vp, _vp, _vp, C.POINTER(BaMapReport)]),
+    "lcm_map_params_default": (None, [C.POINTER(MapParams)]),
+    "lcm_map_median_displacement": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
+    "lcm_map_triangulate_pairs": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.POINTER(MapParams), _vp, _vp, _vp]),
+    "lcm_map_merge": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp,
+                                 C.c_int, _vp, _i32p, _i32p]),
+    "lcm_map_add_keyframe": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.POINTER(MapParams),
+                                        C.POINTER(EpiParams), C.POINTER(LoParams), C.POINTER(PoseParams), _vp, C.c_int, _vp, C.c_int, _vp,
+                                        C.POINTER(MapKeyframeReport)]),
+    "lcm_map_db_track": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.POINTER(EpiParams), C.POINTER(LoParams), C.POINTER(PoseParams), _vp, _vp,
+                                    _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(MapParams),
+                                    _vp, C.c_int, _vp, C.c_int, _vp, C.POINTER(MapKeyframeReport)]),
     "lcm_query_scores": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _i32p]),
     "lcm_query_submit": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _i32p]),
     "lcm_query_collect": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i32p]),
@@ -642,6 +680,18 @@ def ba_add_loop_observations(matches, mask, past_table, curr_table, curr_kp, cur
     _check(load_library().lcm_ba_add_loop_observations(_ptr(m), _ptr(k), len(m), _ptr(past), len(past), _ptr(curr_table), _ptr(kp), len(kp),
                                                        curr, n_points, _ptr(out), len(o), len(out), C.byref(n)))
     return out[:len(o) + n.value], n.value
+
+
+def default_map_params(**over) -> MapParams:
+    """lcm_map_params_default (K zero, min_parallax_deg 1, max_reproj 4, min_depth 0.1, max_depth 50, min_displacement 20,
+    max_displacement 150, min_inlier_ratio 0.3, min_tracked 100, min_inliers 50, min_pose_inliers 10) with any field given by name."""
+    p = MapParams()
+    load_library().lcm_map_params_default(C.byref(p))
+    for k, v in over.items():
+        if k not in _MAP_FIELDS:
+            raise TypeError(f"lcm_map_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
 
 
 def _point_pairs(pts) -> np.ndarray:
@@ -1487,6 +1537,91 @@ class Matcher:
         return po[:len(p)], xo[:rep.n_points], oo[:rep.n_obs], table[:len(x)], rep
 
     # -- loop search -------------------------------------------------------------------------------
+    # -- before the loop: the map (lcm_map_*) --
+    def map_median_displacement(self, pts, offsets) -> np.ndarray:
+        """computeMedianDisplacement per pair of host point pairs float32[total, 4] in the offsets layout: float64[n_pairs]."""
+        offs = np.ascontiguousarray(offsets, np.uintp)
+        n = len(offs) - 1
+        p = _point_pairs(pts)
+        assert n >= 0 and len(p) >= int(offs[n])
+        out = np.zeros(max(n, 1), np.float64)
+        _check(self._lib.lcm_map_median_displacement(self._h, _ptr(p), offs.ctypes.data_as(_vp), n, _ptr(out)))
+        return out[:n]
+
+    def map_triangulate_pairs(self, pts, offsets, poses1, poses2, mp: MapParams, mask=None):
+        """Triangulation and filters of every record of every pair: (MAP_TRI_DTYPE[total], uint8[total] statuses,
+        MAP_PAIR_INFO_DTYPE[n_pairs]).  poses1 / poses2: PGO_POSE_DTYPE[n_pairs]; mask: uint8[total] or None (every record)."""
+        offs = np.ascontiguousarray(offsets, np.uintp)
+        n = len(offs) - 1
+        p = _point_pairs(pts)
+        total = int(offs[n])
+        p1, p2 = np.ascontiguousarray(poses1, PGO_POSE_DTYPE), np.ascontiguousarray(poses2, PGO_POSE_DTYPE)
+        k = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        assert len(p) >= total and len(p1) == n and len(p2) == n and (k is None or len(k) >= total)
+        tri, status, info = np.zeros(max(total, 1), MAP_TRI_DTYPE), np.zeros(max(total, 1), np.uint8), np.zeros(max(n, 1), MAP_PAIR_INFO_DTYPE)
+        _check(self._lib.lcm_map_triangulate_pairs(self._h, _ptr(p), offs.ctypes.data_as(_vp), n, _ptr(k), _ptr(p1), _ptr(p2), _ref(mp),
+                                                   _ptr(tri), _ptr(status), _ptr(info)))
+        return tri[:total], status[:total], info[:n]
+
+    def map_merge(self, matches, pts, tri, status, kf1: int, kf2: int, table1, table2, n_points: int, cap_points: Optional[int] = None,
+                  cap_obs: Optional[int] = None):
+        """lcm_map_merge: (BA_POINT_DTYPE[n_new], BA_OBS_DTYPE[2 n_new + n_merged], uint8[n] statuses, n_new, n_merged); table1 and
+        table2 (int32, C-contiguous) are updated in place."""
+        m = np.ascontiguousarray(matches, DMATCH_DTYPE)
+        n = len(m)
+        p, t, s = _point_pairs(pts), np.ascontiguousarray(tri, MAP_TRI_DTYPE), np.ascontiguousarray(status, np.uint8)
+        assert len(p) == n and len(t) == n and len(s) == n
+        for tab in (table1, table2):
+            assert tab.dtype == np.int32 and tab.flags["C_CONTIGUOUS"]
+        cp, co = n if cap_points is None else cap_points, 2 * n if cap_obs is None else cap_obs
+        points, obs, out = np.zeros(max(cp, 1), BA_POINT_DTYPE), np.zeros(max(co, 1), BA_OBS_DTYPE), np.zeros(max(n, 1), np.uint8)
+        a, b = C.c_int32(0), C.c_int32(0)
+        _check(self._lib.lcm_map_merge(self._h, _ptr(m), _ptr(p), _ptr(t), _ptr(s), n, kf1, kf2, _ptr(table1), len(table1), _ptr(table2),
+                                       len(table2), n_points, _ptr(points), cp, _ptr(obs), co, _ptr(out), C.byref(a), C.byref(b)))
+        return points[:a.value], obs[:2 * a.value + b.value], out[:n], a.value, b.value
+
+    def map_add_keyframe(self, matches, pts, kf_last: int, pose_last, table_last, kf_new: int, table_new, n_points: int, mp: MapParams,
+                         ep: EpiParams, lp: Optional[LoParams] = None, pp: Optional[PoseParams] = None, cap_points: Optional[int] = None,
+                         cap_obs: Optional[int] = None):
+        """lcm_map_add_keyframe: (MapKeyframeReport, BA_POINT_DTYPE[n_new], BA_OBS_DTYPE[new observations], uint8[n] statuses); the
+        tables (int32, C-contiguous) are updated in place when the verdict is MAP_KEYFRAME.  pose_last: PGO_POSE_DTYPE[1]."""
+        m = np.ascontiguousarray(matches, DMATCH_DTYPE)
+        n = len(m)
+        p, pose = _point_pairs(pts), np.ascontiguousarray(pose_last, PGO_POSE_DTYPE).reshape(1)
+        assert len(p) == n
+        for tab in (table_last, table_new):
+            assert tab.dtype == np.int32 and tab.flags["C_CONTIGUOUS"]
+        cp, co = n if cap_points is None else cap_points, 2 * n if cap_obs is None else cap_obs
+        points, obs, out = np.zeros(max(cp, 1), BA_POINT_DTYPE), np.zeros(max(co, 1), BA_OBS_DTYPE), np.zeros(max(n, 1), np.uint8)
+        rep = MapKeyframeReport()
+        _check(self._lib.lcm_map_add_keyframe(self._h, _ptr(m), _ptr(p), n, kf_last, _ptr(pose), _ptr(table_last), len(table_last), kf_new,
+                                              _ptr(table_new), len(table_new), n_points, _ref(mp), _ref(ep), _ref(lp), _ref(pp), _ptr(points),
+                                              cp, _ptr(obs), co, _ptr(out), C.byref(rep)))
+        return rep, points[:rep.n_new], obs[:2 * rep.n_new + rep.n_merged], out[:n]
+
+    def map_db_track(self, last_slot: int, curr_slot: int, ratio: float, kf_last: int, pose_last, table_last, kf_new: int, table_new,
+                     n_points: int, mp: MapParams, ep: EpiParams, lp: Optional[LoParams] = None, pp: Optional[PoseParams] = None,
+                     cap: Optional[int] = None):
+        """lcm_map_db_track on the stored pair (last_slot, curr_slot): (lists, report, points, observations, statuses) where lists is
+        the dict of lcm_pose_db_verify_pairs's outputs (results, pose_results, info, out, pts, mask, pose_mask, offsets)."""
+        cap = self.l2_db_rows(last_slot) if cap is None else cap
+        pose = np.ascontiguousarray(pose_last, PGO_POSE_DTYPE).reshape(1)
+        for tab in (table_last, table_new):
+            assert tab.dtype == np.int32 and tab.flags["C_CONTIGUOUS"]
+        res, pres, info = np.zeros(1, EPI_RESULT_DTYPE), np.zeros(1, POSE_RESULT_DTYPE), np.zeros(1, LO_INFO_DTYPE)
+        out, pts = np.zeros(max(cap, 1), DMATCH_DTYPE), np.zeros((max(cap, 1), 4), np.float32)
+        mask, pmask = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
+        offs = np.zeros(2, np.uintp)
+        points, obs, status = np.zeros(max(cap, 1), BA_POINT_DTYPE), np.zeros(max(2 * cap, 1), BA_OBS_DTYPE), np.zeros(max(cap, 1), np.uint8)
+        rep = MapKeyframeReport()
+        _check(self._lib.lcm_map_db_track(self._h, last_slot, curr_slot, ratio, _ref(ep), _ref(lp), _ref(pp), _ptr(res), _ptr(info), _ptr(pres),
+                                          _ptr(out), _ptr(pts), _ptr(mask), _ptr(pmask), cap, offs.ctypes.data_as(_vp), kf_last, _ptr(pose),
+                                          _ptr(table_last), kf_new, _ptr(table_new), n_points, _ref(mp), _ptr(points), cap, _ptr(obs), 2 * cap,
+                                          _ptr(status), C.byref(rep)))
+        n = int(offs[1])
+        lists = dict(results=res, pose_results=pres, info=info, out=out[:n], pts=pts[:n], mask=mask[:n], pose_mask=pmask[:n], offsets=offs)
+        return lists, rep, points[:rep.n_new], obs[:2 * rep.n_new + rep.n_merged], status[:n]
+
     def query_scores(self, query, query_frame_id: int) -> Tuple[np.ndarray, np.ndarray]:
         q = _rows(query)
         cap = max(len(self), 1)

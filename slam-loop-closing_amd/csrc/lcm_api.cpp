@@ -233,6 +233,9 @@ void lcm_destroy(lcm_handle* h) {
     (void)hipFree(h->pose.d_E); (void)hipFree(h->pose.d_mask_in); (void)hipFree(h->pose.d_cand); (void)hipFree(h->pose.d_res); (void)hipFree(h->pose.d_mask);
     (void)hipFree(h->pgo.d_in); (void)hipFree(h->pgo.d_work);
     (void)hipFree(h->ba.d_map);
+    (void)hipFree(h->map.d_pairs); (void)hipFree(h->map.d_counts); (void)hipFree(h->map.d_median); (void)hipFree(h->map.d_mask);
+    (void)hipFree(h->map.d_tri); (void)hipFree(h->map.d_status); (void)hipFree(h->map.d_matches); (void)hipFree(h->map.d_tab);
+    (void)hipFree(h->map.d_blocks); (void)hipFree(h->map.d_points); (void)hipFree(h->map.d_obs); (void)hipFree(h->map.d_status_out);
     (void)hipFree(h->lo.d_seeds); (void)hipFree(h->lo.d_info); (void)hipFree(h->lo.d_models); (void)hipFree(h->lo.d_seam);
     for (QuerySlot& q : h->qslots) {
         (void)hipFree(q.d_query); (void)hipFree(q.d_scores); (void)hipFree(q.d_dist); (void)hipFree(q.d_meta);

@@ -13,6 +13,7 @@
 //   lcm_lo.cpp         local optimisation of the RANSAC's best hypotheses (lcm_lo_*)
 //   lcm_pgo.cpp        pose-graph Gauss-Newton correction of the closed loop (lcm_pgo_*)
 //   lcm_ba.cpp         alternating bundle adjustment and outlier removal after the loop (lcm_ba_*)
+//   lcm_map.cpp        the map before the loop: keyframe gates, triangulation, filters and merge (lcm_map_*)
 //   lcm_verify.cpp     the three as one staged pipeline over a VerifyPlan (lcm_verify_host.h); the store's and the host-list forms
 // Not installed; the public surface is include/lcm.h.
 #pragma once
@@ -154,6 +155,8 @@ struct Plan {            // cached work list of one bulk call shape
 };
 
 }  // namespace lcm
+
+namespace lcm { struct MapPair; struct MapTri; struct MapPoint; struct MapObs; }    // lcm_map_device.h
 
 using lcm::FrameMeta;
 using lcm::Plan;
@@ -311,6 +314,22 @@ struct lcm_handle {
     struct BaScratch {
         uint8_t* d_map = nullptr;     size_t d_map_n = 0;
     } ba;
+    // the map before the loop (lcm_map.cpp): the per-pair plans, counts and medians, a host call's mask, the records' results, and
+    // a merge's matches, tables ([table1 | table2 | winner]), block counts ([accepted + total | new + total]) and outputs
+    struct MapScratch {
+        lcm::MapPair* d_pairs = nullptr;   size_t d_pairs_n = 0;
+        uint32_t* d_counts = nullptr;      size_t d_counts_n = 0;
+        double* d_median = nullptr;        size_t d_median_n = 0;
+        uint8_t* d_mask = nullptr;         size_t d_mask_n = 0;
+        lcm::MapTri* d_tri = nullptr;      size_t d_tri_n = 0;
+        uint8_t* d_status = nullptr;       size_t d_status_n = 0;
+        uint4* d_matches = nullptr;        size_t d_matches_n = 0;
+        int32_t* d_tab = nullptr;          size_t d_tab_n = 0;
+        uint32_t* d_blocks = nullptr;      size_t d_blocks_n = 0;
+        lcm::MapPoint* d_points = nullptr; size_t d_points_n = 0;
+        lcm::MapObs* d_obs = nullptr;      size_t d_obs_n = 0;
+        uint8_t* d_status_out = nullptr;   size_t d_status_out_n = 0;
+    } map;
     lcm_launch_info info{};
     bool info_pending = false;
 };
@@ -517,6 +536,38 @@ int verify_enqueue(lcm_handle* h, const VerifyPlan& plan, const uint4* d_pts, co
 int verify_download(lcm_handle* h, const VerifyPlan& plan, size_t n_pairs, size_t total);
 // lcm_epi_verify_pairs / lcm_lo_verify_pairs: a plan without the pose stage over host point pairs; lp as the caller gave it
 int verify_pairs(lcm_handle* h, const lcm_point_pair* pts, const size_t* offsets, int n_pairs, VerifyPlan* plan, const lcm_lo_params* lp);
+// ---- lcm_map.cpp: the map's stages over records that are on the device; every *_enqueue works on h's stream and does not wait
+// k_map_median: pair p's median -> h->map.d_median[p]
+int map_median_enqueue(lcm_handle* h, const uint4* d_pts, const uint64_t* d_off, size_t n_pairs);
+// k_map_triangulate: `pairs` (host, n_pairs plans of lcm_map_host.h; read until the caller has waited), d_mask (NULL: all) one byte
+// per record; records -> h->map.d_tri / d_status, MAP_STATUSES counts per pair -> h->map.d_counts
+int map_tri_enqueue(lcm_handle* h, const uint4* d_pts, const uint64_t* d_off, size_t n_pairs, uint32_t max_n, size_t total,
+                    const uint8_t* d_mask, const MapPair* pairs, const lcm_map_params& mp);
+// One merge: the n records' matches, pixels, results and statuses on the device, the tables and the outputs the caller's (host)
+struct MapMergeIO {
+    const uint4* d_matches; const uint4* d_pts; const MapTri* d_tri; const uint8_t* d_status; uint32_t n;
+    int kf1, kf2; int32_t* table1; int n_kp1; int32_t* table2; int n_kp2; int n_points;
+    lcm_ba_point* points_out; int cap_points; lcm_ba_obs* obs_out; int cap_obs; uint8_t* status_out;     // status_out may be NULL
+};
+// k_map_merge_count, two k_block_scan; the two totals come back and decide about the room (LCM_ERR_CAPACITY, *n_new / *n_merged
+// set, nothing else written); then k_map_merge_emit into h->map's buffers.  Waits once, after the counts.  map_merge_download:
+// the points, observations, statuses and both tables to the caller's buffers, enqueued.
+int map_merge_run(lcm_handle* h, const MapMergeIO& io, int* n_new, int* n_merged, uint32_t* launches);
+int map_merge_download(lcm_handle* h, const MapMergeIO& io, int n_new, int n_merged);
+// What lcm_map_add_keyframe is given about the map
+struct MapTrack {
+    const lcm_map_params* mp; int kf_last, kf_new; const lcm_pgo_pose* pose_last; int32_t* table_last; int n_kp_last; int32_t* table_new;
+    int n_kp_new; int n_points; lcm_ba_point* points_out; int cap_points; lcm_ba_obs* obs_out; int cap_obs; uint8_t* status_out;
+    lcm_map_keyframe_report* report;
+};
+// h, the report, mp, the last pose, the counts, the buffers and the tables' entries (LCM_ERR_INVALID_ARG and the message otherwise)
+int map_track_checked(lcm_handle* h, const MapTrack& t, int n_matches);
+// behind a verification with the pose stage over ONE pair, enqueued and not yet read (the pose record is h->pose.d_res[0], its
+// mask h->pose.d_mask): the median, the gates, the triangulation and the merge; waits; *t.report and the map's outputs written
+int map_track_stages(lcm_handle* h, const MapTrack& t, const uint4* d_pts, const uint64_t* d_off, const uint4* d_matches, uint32_t n,
+                     uint32_t* launches);
+int map_keyframe_stages(lcm_handle* h, const MapTrack& t, const uint4* d_pts, const uint64_t* d_off, const uint4* d_matches,
+                        const uint8_t* d_pose_mask, uint32_t n, const lcm_pose_result& pr, uint32_t* launches);
 }  // namespace lcm
 
 namespace {

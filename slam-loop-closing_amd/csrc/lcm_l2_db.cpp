@@ -5,6 +5,8 @@
 // through lcm_verify.cpp's pipeline; the best loop is chosen on the host).  Shared state and helpers: lcm_internal.h.
 #include "lcm_internal.h"
 
+#include <functional>
+
 namespace {
 
 constexpr int TILE = lcm::L2_TILE_ROWS, ROW = LCM_SIFT_BYTES;
@@ -276,8 +278,12 @@ static_assert(sizeof(size_t) == sizeof(uint64_t) && sizeof(lcm_dmatch) == sizeof
 // plan != NULL (checked, with pts): the plan's stages (lcm_verify.cpp: the RANSAC, then the local optimisation and the pose
 // recovery where wanted) run on the point records as soon as k_l2_emit has written them, pair p of the call seeded with p;
 // their kernels count into `launches` and into the aux events' span.
+// after != NULL (with a plan): called behind the plan's stages with the device's point records, offsets and match records and the
+// record count, before anything of the lists is copied back; it may wait for the stream, adds its launches and may refuse.
+using StoreAfter = std::function<int(const uint4* d_pts, const uint64_t* d_off, const uint4* d_rec, size_t total, uint32_t* launches)>;
 int store_lists(lcm_handle* h, const int* rows, const std::vector<L2Pair>& live, const std::vector<int>& job_of, double ratio,
-                lcm_dmatch* out, lcm_point_pair* pts, size_t cap, size_t* offsets, const VerifyPlan* plan = nullptr) {
+                lcm_dmatch* out, lcm_point_pair* pts, size_t cap, size_t* offsets, const VerifyPlan* plan = nullptr,
+                const StoreAfter* after = nullptr) {
     const size_t n_pairs = job_of.size();
     if (live.empty()) {
         std::fill(offsets, offsets + n_pairs + 1, (size_t)0);
@@ -334,6 +340,15 @@ int store_lists(lcm_handle* h, const int* rows, const std::vector<L2Pair>& live,
         for (size_t p = 0; p < n_pairs; ++p) max_n = std::max(max_n, (uint32_t)(offsets[p + 1] - offsets[p]));
         rc = lcm::verify_enqueue(h, *plan, s.d_rec_pts, s.d_offsets, n_pairs, max_n, total, &launches); if (rc) return rc;
         h->info.launches += launches;
+        if (after) {
+            rc = (*after)(s.d_rec_pts, s.d_offsets, s.d_rec, total, &launches);
+            h->info.launches += launches;
+            if (rc) {
+                HIP_TRY(hipEventRecord(h->ev_aux_stop, h->stream));
+                h->aux_pending = true;
+                return rc;
+            }
+        }
     }
     HIP_TRY(hipEventRecord(h->ev_aux_stop, h->stream));
     h->aux_pending = true;
@@ -359,7 +374,7 @@ int check_slot_pts(const L2Store& d, int slot) {
 }
 
 int l2_db_match_points_impl(lcm_handle* h, const lcm_pair_ref* slots, int n_pairs, double ratio, lcm_dmatch* out, lcm_point_pair* pts,
-                            size_t cap, size_t* offsets, const VerifyPlan* plan = nullptr) {
+                            size_t cap, size_t* offsets, const VerifyPlan* plan = nullptr, const StoreAfter* after = nullptr) {
     if (!h || n_pairs < 0 || !offsets || (n_pairs > 0 && !slots)) return fail(LCM_ERR_INVALID_ARG, "bad argument");
     if (plan) { const int rc = plan_checked(*plan, pts, (size_t)n_pairs); if (rc) return rc; }
     offsets[0] = 0;
@@ -373,7 +388,7 @@ int l2_db_match_points_impl(lcm_handle* h, const lcm_pair_ref* slots, int n_pair
         return check_slot_pts(d, t);
     });
     if (rc) return rc;
-    return store_lists(h, d.rows.data(), live, job_of, ratio, out, pts, cap, offsets, plan);
+    return store_lists(h, d.rows.data(), live, job_of, ratio, out, pts, cap, offsets, plan, after);
 }
 
 int l2_db_detect_loops_points_impl(lcm_handle* h, int curr, const uint8_t* query, const float* query_pts, int nq, const uint8_t* skip,
@@ -435,6 +450,31 @@ int db_verify_pairs(lcm_handle* h, const lcm_pair_ref* slots, int n_pairs, doubl
                     size_t* offsets, VerifyPlan* plan, const lcm_lo_params* lp, const lcm_pose_params* pp) {
     const int rc = lcm::verify_params_checked(plan, lp, pp); if (rc) return rc;
     return l2_db_match_points_impl(h, slots, n_pairs, ratio, out, pts, cap, offsets, plan);
+}
+
+// lcm_map_db_track: lcm_{pose,lo}_db_verify_pairs on the one pair {last, curr}, with the map's stages (lcm_map.cpp) behind the
+// verification on the records it left on the device.  A list by knnMatch names every query row once and only rows of the two
+// slots, so what lcm_map_merge checks about a host list holds by construction; the tables and the buffers are checked here.
+int map_db_track_impl(lcm_handle* h, int last_slot, int curr_slot, double ratio, lcm_dmatch* out, lcm_point_pair* pts, size_t cap,
+                      size_t* offsets, VerifyPlan* plan, const lcm_lo_params* lp, const lcm_pose_params* pp, lcm::MapTrack t) {
+    if (!h) return fail(LCM_ERR_INVALID_ARG, "bad argument");
+    int rc = check_slot(h, last_slot); if (rc) return rc;
+    rc = check_slot(h, curr_slot); if (rc) return rc;
+    t.n_kp_last = h->l2db.rows[(size_t)last_slot]; t.n_kp_new = h->l2db.rows[(size_t)curr_slot];
+    rc = lcm::map_track_checked(h, t, 0); if (rc) return rc;
+    rc = lcm::verify_params_checked(plan, lp, pp); if (rc) return rc;
+    const lcm_pair_ref slots{last_slot, curr_slot};
+    bool ran = false;
+    const StoreAfter after = [&](const uint4* d_pts, const uint64_t* d_off, const uint4* d_rec, size_t total, uint32_t* launches) {
+        ran = true;
+        return lcm::map_track_stages(h, t, d_pts, d_off, d_rec, (uint32_t)total, launches);
+    };
+    rc = l2_db_match_points_impl(h, &slots, 1, ratio, out, pts, cap, offsets, plan, &after); if (rc) return rc;
+    if (!ran) {                                     // a slot without rows: an empty list, nothing was launched
+        uint32_t launches = 0;
+        return lcm::map_track_stages(h, t, nullptr, nullptr, nullptr, 0, &launches);
+    }
+    return LCM_OK;
 }
 
 // lcm_{pose,lo}_db_detect_loops: the same, then `best`; the best loop among the verified candidates is chosen on the host
@@ -555,6 +595,19 @@ int lcm_lo_db_verify_pairs(lcm_handle* h, const lcm_pair_ref* slots, int n_pairs
     return guarded([&] {
         VerifyPlan w{ep, true, true, results, mask, info, pose_results, pose_mask};
         return db_verify_pairs(h, slots, n_pairs, ratio, out, pts, cap, offsets, &w, lp, pp);
+    });
+}
+int lcm_map_db_track(lcm_handle* h, int last_slot, int curr_slot, double ratio, const lcm_epi_params* ep, const lcm_lo_params* lp,
+                     const lcm_pose_params* pp, lcm_epi_result* result, lcm_lo_info* info, lcm_pose_result* pose_result, lcm_dmatch* out,
+                     lcm_point_pair* pts, uint8_t* mask, uint8_t* pose_mask, size_t cap, size_t* offsets, int kf_last,
+                     const lcm_pgo_pose* pose_last, int32_t* table_last, int kf_new, int32_t* table_new, int n_points,
+                     const lcm_map_params* mp, lcm_ba_point* points_out, int cap_points, lcm_ba_obs* obs_out, int cap_obs,
+                     uint8_t* status_out, lcm_map_keyframe_report* report) {
+    return guarded([&] {
+        VerifyPlan w{ep, lp != nullptr, true, result, mask, info, pose_result, pose_mask};
+        const lcm::MapTrack t{mp, kf_last, kf_new, pose_last, table_last, 0, table_new, 0, n_points, points_out, cap_points, obs_out, cap_obs,
+                              status_out, report};
+        return map_db_track_impl(h, last_slot, curr_slot, ratio, out, pts, cap, offsets, &w, lp, pp, t);
     });
 }
 int lcm_lo_db_detect_loops(lcm_handle* h, int curr, const uint8_t* query, const float* query_pts, int nq, const uint8_t* skip,
