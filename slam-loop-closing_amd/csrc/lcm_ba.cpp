@@ -7,11 +7,11 @@
 
 #include "lcm_ba_host.h"
 
-static_assert(sizeof(lcm_ba_point) == 24 && sizeof(lcm::BaPoint) == 24 && sizeof(lcm_ba_obs) == 24 && sizeof(lcm::BaObs) == 24 &&
+static_assert(sizeof(lcm_ba_point) == 24 && sizeof(lcm::Point3) == 24 && sizeof(lcm_ba_obs) == 24 && sizeof(lcm::Observation) == 24 &&
               sizeof(lcm_ba_elem_info) == 24 && sizeof(lcm::BaElemInfo) == 24 && sizeof(lcm_ba_params) == 112 &&
-              sizeof(lcm_ba_info) == 184 && sizeof(lcm_ba_map_report) == 56 && sizeof(lcm::BaPose) == sizeof(lcm_pgo_pose), "record sizes");
-static_assert(offsetof(lcm_ba_obs, point) == 4 && offsetof(lcm::BaObs, point) == 4 && offsetof(lcm_ba_obs, u) == 8 && offsetof(lcm::BaObs, u) == 8 &&
-              offsetof(lcm_ba_obs, v) == 16 && offsetof(lcm::BaObs, v) == 16, "observation layout");
+              sizeof(lcm_ba_info) == 184 && sizeof(lcm_ba_map_report) == 56, "record sizes");
+static_assert(offsetof(lcm_ba_obs, point) == 4 && offsetof(lcm::Observation, point) == 4 && offsetof(lcm_ba_obs, u) == 8 &&
+              offsetof(lcm::Observation, u) == 8 && offsetof(lcm_ba_obs, v) == 16 && offsetof(lcm::Observation, v) == 16, "observation layout");
 static_assert(offsetof(lcm_ba_elem_info, cost) == 8 && offsetof(lcm::BaElemInfo, cost) == 8 && offsetof(lcm_ba_elem_info, iterations) == 16 &&
               offsetof(lcm::BaElemInfo, iterations) == 16 && offsetof(lcm_ba_elem_info, status) == 20 && offsetof(lcm::BaElemInfo, status) == 20,
               "element info layout");
@@ -42,8 +42,6 @@ struct BaOut {                                // what a mode returns; the pointe
     lcm_ba_info* info = nullptr;
     uint8_t* flags = nullptr; double* max_err = nullptr; double* threshold = nullptr; int* n_outliers = nullptr;
 };
-
-size_t up16(size_t v) { return (v + 15) / 16 * 16; }
 
 bool ba_outputs_missing(BaMode mode, const BaOut& o) {
     switch (mode) {
@@ -107,8 +105,8 @@ int ba_run(lcm_handle* h, const BaMap& m, const lcm_ba_params* pp_in, BaMode mod
     if (seam) HIP_TRY(hipMemsetAsync(d + o_seam, 0, total - o_seam, h->stream));
 
     lcm::BaArgs a{};
-    a.poses = reinterpret_cast<lcm::BaPose*>(d + o_poses); a.points = reinterpret_cast<lcm::BaPoint*>(d + o_points);
-    a.valid = d + o_valid; a.obs = reinterpret_cast<const lcm::BaObs*>(d + o_obs);
+    a.poses = reinterpret_cast<lcm::Pose*>(d + o_poses); a.points = reinterpret_cast<lcm::Point3*>(d + o_points);
+    a.valid = d + o_valid; a.obs = reinterpret_cast<const lcm::Observation*>(d + o_obs);
     a.cam_off = reinterpret_cast<const uint32_t*>(d + o_cam_off); a.cam_obs = reinterpret_cast<const uint32_t*>(d + o_cam_obs);
     a.pt_off = reinterpret_cast<const uint32_t*>(d + o_pt_off); a.pt_obs = reinterpret_cast<const uint32_t*>(d + o_pt_obs);
     a.cam_info = reinterpret_cast<lcm::BaElemInfo*>(d + o_cam_info); a.pt_info = reinterpret_cast<lcm::BaElemInfo*>(d + o_pt_info);
@@ -121,7 +119,7 @@ int ba_run(lcm_handle* h, const BaMap& m, const lcm_ba_params* pp_in, BaMode mod
         a.seam_g = reinterpret_cast<double*>(d + o_g); a.seam_dp = reinterpret_cast<double*>(d + o_dp);
     }
     a.n_cams = (uint32_t)NC; a.n_points = (uint32_t)NP; a.n_obs = (uint32_t)NO; a.n_partials = (uint32_t)n_partials;
-    a.K = lcm::BaCamera{pp.fx, pp.fy, pp.cx, pp.cy};
+    a.K = lcm::Camera{pp.fx, pp.fy, pp.cx, pp.cy};
     a.eps = pp.eps; a.damping = pp.damping; a.min_update = pp.min_update; a.outlier_px = pp.outlier_px;
     a.inner_iters = seam ? 1 : pp.inner_iters; a.min_cam_obs = pp.min_cam_obs; a.min_point_obs = pp.min_point_obs;
     double threshold = 0.0;

@@ -1,9 +1,9 @@
 // lcm_ba.hip — the reference's alternatingBundleAdjustment (src/main.cpp:905-943: refineCameraPoseGN :632-743, refinePointGN
 // :757-858), computeReprojectionError (:871-896) and the outlier flags of :1563-1619 on the device, with every step's arithmetic
-// defined in lcm_ba_device.h.  With the points fixed every camera is independent of every other, with the poses fixed so is every
-// point: a phase runs all its elements at once and gives what the reference's sequential loops give.  No floating-point atomic
-// anywhere: every sum has one owner and a fixed order, so the same call gives the same bytes, and an element's k-th iteration
-// depends neither on min_update nor on inner_iters.
+// defined in lcm_ba_device.h and, where other stages share it, lcm_geom_device.h.  With the points fixed every camera is
+// independent of every other, with the poses fixed so is every point: a phase runs all its elements at once and gives what the
+// reference's sequential loops give.  No floating-point atomic anywhere: every sum has one owner and a fixed order, so the same
+// call gives the same bytes, and an element's k-th iteration depends neither on min_update nor on inner_iters.
 //
 // k_ba_cameras   one workgroup of 256 threads per camera, every inner iteration inside the kernel.  Per iteration lanes 0 .. 6
 //                build the seven distinct rotations of the thirteen parameter vectors into LDS (p, p + eps e_k and p - eps e_k for
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(256) void k_ba_cameras(BaArgs a) {
         double R[9], r[3];
 #pragma unroll
         for (int k = 0; k < 9; ++k) R[k] = a.poses[cam].R[k];
-        const bool ok = pgo_log(R, r);
+        const bool ok = so3_log(R, r);
 #pragma unroll
         for (int k = 0; k < 3; ++k) { par[k] = r[k]; par[3 + k] = a.poses[cam].t[k]; }
         word[0] = ok; word[1] = 0;
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void k_ba_cameras(BaArgs a) {
             double r[3] = {par[0], par[1], par[2]}, R[9];
             if (tid >= 1 && tid <= 3) r[tid - 1] = r[tid - 1] + a.eps;
             if (tid >= 4) r[tid - 4] = r[tid - 4] - a.eps;
-            pgo_exp(r, R);
+            so3_exp(r, R);
 #pragma unroll
             for (int k = 0; k < 9; ++k) rot[9 * tid + k] = R[k];
         }
@@ -112,13 +112,13 @@ __global__ __launch_bounds__(256) void k_ba_cameras(BaArgs a) {
         for (int k = 0; k < 6; ++k) g[k] = 0.0;
         for (uint32_t i = e0 + tid; i < e1; i += BA_CAMERA_THREADS) {
             const uint32_t oi = a.cam_obs[i];
-            const BaObs ob = a.obs[oi];
-            const BaPoint P = a.points[ob.point];
+            const Observation ob = a.obs[oi];
+            const Point3 P = a.points[ob.point];
             const double X[3] = {P.x, P.y, P.z};
             double R[9], Y0[3], Y[3], Xc[3], r[2], rp[2], rm[2], col[2], Ju[6], Jv[6];
 #pragma unroll
             for (int k = 0; k < 9; ++k) R[k] = rot[k];
-            ba_rotate(R, X, Y0);
+            mat3_apply(R, X, Y0);
 #pragma unroll
             for (int k = 0; k < 3; ++k) Xc[k] = Y0[k] + t[k];
             ba_residual(a.K, Xc, ob.u, ob.v, r);
@@ -126,13 +126,13 @@ __global__ __launch_bounds__(256) void k_ba_cameras(BaArgs a) {
             for (int c = 0; c < 3; ++c) {                              // the rotation columns: their own R, the translation of p
 #pragma unroll
                 for (int k = 0; k < 9; ++k) R[k] = rot[9 * (1 + c) + k];
-                ba_rotate(R, X, Y);
+                mat3_apply(R, X, Y);
 #pragma unroll
                 for (int k = 0; k < 3; ++k) Xc[k] = Y[k] + t[k];
                 ba_residual(a.K, Xc, ob.u, ob.v, rp);
 #pragma unroll
                 for (int k = 0; k < 9; ++k) R[k] = rot[9 * (4 + c) + k];
-                ba_rotate(R, X, Y);
+                mat3_apply(R, X, Y);
 #pragma unroll
                 for (int k = 0; k < 3; ++k) Xc[k] = Y[k] + t[k];
                 ba_residual(a.K, Xc, ob.u, ob.v, rm);
@@ -181,12 +181,12 @@ __global__ __launch_bounds__(256) void k_ba_cameras(BaArgs a) {
                 if (k < 21) H[k] = s; else if (k < 27) g[k - 21] = s; else cost = s;
             }
             info.cost = cost;
-            const bool ok = ba_solve6(H, g, a.damping, dp);
+            const bool ok = solve_damped<6>(H, g, a.damping, dp);
             if (a.seam_H) {
 #pragma unroll
                 for (int r = 0; r < 6; ++r)
 #pragma unroll
-                    for (int c = 0; c < 6; ++c) a.seam_H[36 * (size_t)cam + 6 * r + c] = H[r >= c ? pgo_tri(r, c) : pgo_tri(c, r)];
+                    for (int c = 0; c < 6; ++c) a.seam_H[36 * (size_t)cam + 6 * r + c] = H[r >= c ? tri_index(r, c) : tri_index(c, r)];
 #pragma unroll
                 for (int k = 0; k < 6; ++k) { a.seam_g[6 * (size_t)cam + k] = g[k]; a.seam_dp[6 * (size_t)cam + k] = ok ? dp[k] : 0.0; }
             }
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(256) void k_ba_cameras(BaArgs a) {
     if (tid == 0) {
         const double r[3] = {par[0], par[1], par[2]};
         double R[9];
-        pgo_exp(r, R);
+        so3_exp(r, R);
 #pragma unroll
         for (int k = 0; k < 9; ++k) a.poses[cam].R[k] = R[k];
 #pragma unroll
@@ -240,22 +240,22 @@ __global__ __launch_bounds__(64) void k_ba_points(BaArgs a) {
         for (int k = 0; k < 3; ++k) g[k] = 0.0;
         for (uint32_t i = e0; i < e1; ++i) {
             const uint32_t oi = a.pt_obs[i];
-            const BaObs ob = a.obs[oi];
-            const BaPose& pose = a.poses[ob.cam];
+            const Observation ob = a.obs[oi];
+            const Pose& pose = a.poses[ob.cam];
             double R[9], t[3], Xc[3], r[2], rp[2], rm[2], col[2], Ju[3], Jv[3];
 #pragma unroll
             for (int k = 0; k < 9; ++k) R[k] = pose.R[k];
 #pragma unroll
             for (int k = 0; k < 3; ++k) t[k] = pose.t[k];
-            ba_camera_point(R, t, X, Xc);
+            rigid_apply(R, t, X, Xc);
             ba_residual(a.K, Xc, ob.u, ob.v, r);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 double Xp[3] = {X[0], X[1], X[2]}, Xm[3] = {X[0], X[1], X[2]};
                 Xp[c] = Xp[c] + a.eps; Xm[c] = Xm[c] - a.eps;
-                ba_camera_point(R, t, Xp, Xc);
+                rigid_apply(R, t, Xp, Xc);
                 ba_residual(a.K, Xc, ob.u, ob.v, rp);
-                ba_camera_point(R, t, Xm, Xc);
+                rigid_apply(R, t, Xm, Xc);
                 ba_residual(a.K, Xc, ob.u, ob.v, rm);
                 ba_column(rp, rm, half_inv_eps, col);
                 Ju[c] = col[0]; Jv[c] = col[1];
@@ -268,12 +268,12 @@ __global__ __launch_bounds__(64) void k_ba_points(BaArgs a) {
             ba_accumulate<3>(Ju, Jv, r, H, g, cost);
         }
         info.cost = cost;
-        const bool ok = ba_solve3(H, g, a.damping, dp);
+        const bool ok = solve_damped<3>(H, g, a.damping, dp);
         if (a.seam_H) {
 #pragma unroll
             for (int r = 0; r < 3; ++r)
 #pragma unroll
-                for (int c = 0; c < 3; ++c) a.seam_H[9 * (size_t)p + 3 * r + c] = H[r >= c ? pgo_tri(r, c) : pgo_tri(c, r)];
+                for (int c = 0; c < 3; ++c) a.seam_H[9 * (size_t)p + 3 * r + c] = H[r >= c ? tri_index(r, c) : tri_index(c, r)];
 #pragma unroll
             for (int k = 0; k < 3; ++k) { a.seam_g[3 * (size_t)p + k] = g[k]; a.seam_dp[3 * (size_t)p + k] = ok ? dp[k] : 0.0; }
         }
@@ -299,16 +299,16 @@ __global__ __launch_bounds__(256) void k_ba_error(BaArgs a) {
     const uint32_t tid = threadIdx.x, i = blockIdx.x * BA_ERROR_THREADS + tid;
     double err = 0.0;
     if (i < a.n_obs) {
-        const BaObs ob = a.obs[i];
-        const BaPose& pose = a.poses[ob.cam];
-        const BaPoint P = a.points[ob.point];
+        const Observation ob = a.obs[i];
+        const Pose& pose = a.poses[ob.cam];
+        const Point3 P = a.points[ob.point];
         const double X[3] = {P.x, P.y, P.z};
         double R[9], t[3], Xc[3], r[2];
 #pragma unroll
         for (int k = 0; k < 9; ++k) R[k] = pose.R[k];
 #pragma unroll
         for (int k = 0; k < 3; ++k) t[k] = pose.t[k];
-        ba_camera_point(R, t, X, Xc);
+        rigid_apply(R, t, X, Xc);
         ba_residual(a.K, Xc, ob.u, ob.v, r);
         err = ba_error(r);
         if (a.obs_err) a.obs_err[i] = err;
@@ -336,14 +336,14 @@ __global__ __launch_bounds__(64) void k_ba_outliers(BaArgs a) {
     bool flag = false;
     double worst = 0.0;
     for (uint32_t i = a.pt_off[p]; i < a.pt_off[p + 1]; ++i) {
-        const BaObs ob = a.obs[a.pt_obs[i]];
-        const BaPose& pose = a.poses[ob.cam];
+        const Observation ob = a.obs[a.pt_obs[i]];
+        const Pose& pose = a.poses[ob.cam];
         double R[9], t[3], Xc[3], r[2];
 #pragma unroll
         for (int k = 0; k < 9; ++k) R[k] = pose.R[k];
 #pragma unroll
         for (int k = 0; k < 3; ++k) t[k] = pose.t[k];
-        ba_camera_point(R, t, X, Xc);
+        rigid_apply(R, t, X, Xc);
         if (Xc[2] <= 0.0) { flag = true; continue; }
         ba_residual(a.K, Xc, ob.u, ob.v, r);
         const double err = ba_error(r);

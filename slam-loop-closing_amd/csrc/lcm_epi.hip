@@ -2,7 +2,7 @@
 // the inlier count (src/main.cpp:1395-1400), as a RANSAC whose every step is defined in lcm_epi_device.h: a counter-based
 // sampler, the linear eight-point solver on normalised coordinates, a fixed number of hypotheses, first-of-equals selection.
 // The kernels run on the point records k_l2_emit has just written (lcm_epi_db_*), or on a caller's (lcm_epi_verify_pairs).
-// The pair comes from blockIdx.y, in slices of grid_y_limit() pairs as k_l2_fold's does.
+// The pair comes from blockIdx.y, in slices (launch_y_sliced, lcm_kernels.h) as k_l2_fold's does.
 //
 // k_epi_solve   one lane per (pair, hypothesis), one wave per workgroup: the lane draws its 8 indices, normalises those 8
 //               records, lays the 8 x 9 system into its own column of LDS (72 doubles x 64 lanes: runtime row and column
@@ -123,32 +123,16 @@ __global__ __launch_bounds__(256) void k_epi_mask(EpiArgs a) {
     a.mask[first + i] = in ? 1 : 0;
 }
 
-template <typename K>
-static hipError_t launch_sliced(K kernel, const EpiArgs& a, uint32_t n_pairs, uint32_t grid_x, uint32_t block, hipStream_t st) {
-    if (n_pairs == 0) return hipSuccess;
-    uint32_t lim = 0;
-    hipError_t e = grid_y_limit(&lim);
-    if (e != hipSuccess) return e;
-    EpiArgs s = a;                                             // slices of at most gridDim.y's limit (lcm_kernels.h)
-    for (s.pair_base = 0; s.pair_base < n_pairs; s.pair_base += lim) {
-        hipLaunchKernelGGL(kernel, dim3(grid_x, std::min(lim, n_pairs - s.pair_base)), dim3(block), 0, st, s);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        if (n_pairs - s.pair_base <= lim) break;
-    }
-    return hipSuccess;
-}
-
 hipError_t launch_epi_solve(const EpiArgs& a, uint32_t n_pairs, hipStream_t st) {
-    return launch_sliced(k_epi_solve, a, n_pairs, a.iters / 64u, 64, st);
+    return launch_y_sliced(k_epi_solve, a, &EpiArgs::pair_base, n_pairs, a.iters / 64u, 64, st);
 }
 
 hipError_t launch_epi_score(const EpiArgs& a, uint32_t n_pairs, hipStream_t st) {
-    return launch_sliced(k_epi_score, a, n_pairs, (a.iters + 255u) / 256u, 256, st);
+    return launch_y_sliced(k_epi_score, a, &EpiArgs::pair_base, n_pairs, (a.iters + 255u) / 256u, 256, st);
 }
 
 hipError_t launch_epi_mask(const EpiArgs& a, uint32_t n_pairs, uint32_t max_n, hipStream_t st) {
-    return launch_sliced(k_epi_mask, a, n_pairs, std::max(1u, (max_n + 255u) / 256u), 256, st);
+    return launch_y_sliced(k_epi_mask, a, &EpiArgs::pair_base, n_pairs, std::max(1u, (max_n + 255u) / 256u), 256, st);
 }
 
 }  // namespace lcm

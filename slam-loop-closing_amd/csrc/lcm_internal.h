@@ -70,6 +70,7 @@ constexpr int DEFAULT_MAX_DESC = 2000;  // ORB nfeatures of the reference (READM
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 inline int padded_rows(int n) { return round_up(n, ROW_PAD); }   // rows [n, round_up(n,4)) of a stored frame repeat row n-1
+inline size_t up16(size_t v) { return (v + 15) / 16 * 16; }      // the next 16-byte boundary of an offset in a staging block
 inline uint64_t mix(uint64_t h, uint64_t v) { return h ^ (v + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2)); }
 
 }  // namespace
@@ -156,7 +157,7 @@ struct Plan {            // cached work list of one bulk call shape
 
 }  // namespace lcm
 
-namespace lcm { struct MapPair; struct MapTri; struct MapPoint; struct MapObs; }    // lcm_map_device.h
+namespace lcm { struct MapPair; struct MapTri; struct Point3; struct Observation; }    // lcm_map_device.h, lcm_geom_device.h
 
 using lcm::FrameMeta;
 using lcm::Plan;
@@ -326,8 +327,8 @@ struct lcm_handle {
         uint4* d_matches = nullptr;        size_t d_matches_n = 0;
         int32_t* d_tab = nullptr;          size_t d_tab_n = 0;
         uint32_t* d_blocks = nullptr;      size_t d_blocks_n = 0;
-        lcm::MapPoint* d_points = nullptr; size_t d_points_n = 0;
-        lcm::MapObs* d_obs = nullptr;      size_t d_obs_n = 0;
+        lcm::Point3* d_points = nullptr; size_t d_points_n = 0;
+        lcm::Observation* d_obs = nullptr;      size_t d_obs_n = 0;
         uint8_t* d_status_out = nullptr;   size_t d_status_out_n = 0;
     } map;
     lcm_launch_info info{};

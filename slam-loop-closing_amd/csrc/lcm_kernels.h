@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 namespace lcm {
 
 constexpr int KEY_SHIFT = 22;                       // packed key = dist << 22 | train_idx  (dist <= 256 -> 9 bits)
@@ -129,6 +131,23 @@ struct FoldArgs {
 // once per device and kept): the fold launchers cut a call's pairs into slices of at most that many, one launch each, so
 // that the number of pairs in a call is bounded by its buffers alone.
 hipError_t grid_y_limit(uint32_t* limit);
+// The launch of every kernel whose grid's y is the pair or the job: n of them in slices of at most that limit, one launch each,
+// grid (grid_x, the slice's length), with args.*base = the pair or job of blockIdx.y == 0.  n == 0 launches and asks nothing.
+template <typename Kernel, typename Args>
+hipError_t launch_y_sliced(Kernel kernel, const Args& args, uint32_t Args::*base, uint32_t n, uint32_t grid_x, uint32_t block, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    uint32_t lim = 0;
+    hipError_t e = grid_y_limit(&lim);
+    if (e != hipSuccess) return e;
+    Args s = args;
+    for (s.*base = 0; s.*base < n; s.*base += lim) {
+        hipLaunchKernelGGL(kernel, dim3(grid_x, std::min(lim, n - s.*base)), dim3(block), 0, st, s);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        if (n - s.*base <= lim) break;                             // base + lim may not fit 32 bits
+    }
+    return hipSuccess;
+}
 hipError_t launch_fold_pair_keys(const FoldArgs& a, uint32_t max_nq, hipStream_t st);
 // bytes (rounded up to 16; both buffers must have that room, 16-byte aligned) from PINNED host memory to device memory, by
 // a kernel on `st` instead of a DMA-engine copy (latency-critical small uploads)

@@ -819,17 +819,7 @@ hipError_t grid_y_limit(uint32_t* limit) {
 
 hipError_t launch_fold_pair_keys(const FoldArgs& a, uint32_t max_nq, hipStream_t st) {
     if (a.n_pairs == 0 || max_nq == 0) return hipSuccess;
-    uint32_t lim = 0;
-    hipError_t e = grid_y_limit(&lim);
-    if (e != hipSuccess) return e;
-    FoldArgs s = a;
-    for (s.pair_base = 0; s.pair_base < a.n_pairs; s.pair_base += lim) {
-        hipLaunchKernelGGL(k_fold_pair_keys, dim3((max_nq + 31) / 32, std::min(lim, a.n_pairs - s.pair_base)), dim3(256), 0, st, s);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        if (a.n_pairs - s.pair_base <= lim) break;             // pair_base + lim may not fit 32 bits
-    }
-    return hipSuccess;
+    return launch_y_sliced(k_fold_pair_keys, a, &FoldArgs::pair_base, a.n_pairs, (max_nq + 31) / 32, 256, st);
 }
 
 // Upload by kernel: n16 16-byte words from pinned host memory (mapped into the device's address space) to device memory.

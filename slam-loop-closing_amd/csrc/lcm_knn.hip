@@ -193,17 +193,7 @@ __global__ __launch_bounds__(256) void k_fold_pair_keys2(FoldArgs a) {
 
 hipError_t launch_fold_pair_keys2(const FoldArgs& a, uint32_t max_nq, hipStream_t st) {
     if (a.n_pairs == 0 || max_nq == 0) return hipSuccess;
-    uint32_t lim = 0;
-    hipError_t e = grid_y_limit(&lim);
-    if (e != hipSuccess) return e;
-    FoldArgs s = a;                                            // slices of at most gridDim.y's limit, as launch_fold_pair_keys
-    for (s.pair_base = 0; s.pair_base < a.n_pairs; s.pair_base += lim) {
-        hipLaunchKernelGGL(k_fold_pair_keys2, dim3((max_nq + 31) / 32, std::min(lim, a.n_pairs - s.pair_base)), dim3(256), 0, st, s);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        if (a.n_pairs - s.pair_base <= lim) break;
-    }
-    return hipSuccess;
+    return launch_y_sliced(k_fold_pair_keys2, a, &FoldArgs::pair_base, a.n_pairs, (max_nq + 31) / 32, 256, st);
 }
 
 }  // namespace lcm

@@ -201,17 +201,7 @@ __global__ __launch_bounds__(256) void k_l2_fold(L2FoldArgs a) {
 
 hipError_t launch_l2_fold(const L2FoldArgs& a, uint32_t n_jobs, uint32_t max_nq, hipStream_t st) {
     if (n_jobs == 0 || max_nq == 0) return hipSuccess;
-    uint32_t lim = 0;
-    hipError_t e = grid_y_limit(&lim);
-    if (e != hipSuccess) return e;
-    L2FoldArgs s = a;                                          // slices of at most gridDim.y's limit (lcm_kernels.h)
-    for (s.job_base = 0; s.job_base < n_jobs; s.job_base += lim) {
-        hipLaunchKernelGGL(k_l2_fold, dim3((max_nq + 255) / 256, std::min(lim, n_jobs - s.job_base)), dim3(256), 0, st, s);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        if (n_jobs - s.job_base <= lim) break;
-    }
-    return hipSuccess;
+    return launch_y_sliced(k_l2_fold, a, &L2FoldArgs::job_base, n_jobs, (max_nq + 255) / 256, 256, st);
 }
 
 // ---- rescan of the rows whose second neighbour may share a float root with its rival ----------------------------------

@@ -5,7 +5,7 @@
 //
 // The kernels read final_keys, (D1, idx1, D2, idx2) per query row of every job, and therefore run AFTER k_l2_rescan, which
 // rewrites the rows whose second neighbour may share a float root with a rival.  A job's query rows are cut into blocks of
-// 256 (lcm_kernels.h, L2EmitArgs); the job comes from blockIdx.y, in slices of grid_y_limit() jobs as k_l2_fold's does.
+// 256 (lcm_kernels.h, L2EmitArgs); the job comes from blockIdx.y, in slices (launch_y_sliced) as k_l2_fold's does.
 //
 // k_l2_emit_count    one workgroup per block: the survivors of l2_ratio_pass (lcm_l2_count_device.h: the one verdict, the
 //                    host's bit for bit) among its rows -> blocks[block].  A row without a second neighbour is dropped.
@@ -75,28 +75,14 @@ __global__ __launch_bounds__(256) void k_l2_emit(L2EmitArgs a) {
     }
 }
 
-template <typename K>
-static hipError_t launch_sliced(K kernel, const L2EmitArgs& a, uint32_t n_jobs, uint32_t max_nq, hipStream_t st) {
-    if (n_jobs == 0 || max_nq == 0) return hipSuccess;
-    uint32_t lim = 0;
-    hipError_t e = grid_y_limit(&lim);
-    if (e != hipSuccess) return e;
-    L2EmitArgs s = a;                                          // slices of at most gridDim.y's limit (lcm_kernels.h)
-    for (s.job_base = 0; s.job_base < n_jobs; s.job_base += lim) {
-        hipLaunchKernelGGL(kernel, dim3((max_nq + 255) / 256, std::min(lim, n_jobs - s.job_base)), dim3(256), 0, st, s);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        if (n_jobs - s.job_base <= lim) break;
-    }
-    return hipSuccess;
-}
-
 hipError_t launch_l2_emit_count(const L2EmitArgs& a, uint32_t n_jobs, uint32_t max_nq, hipStream_t st) {
-    return launch_sliced(k_l2_emit_count, a, n_jobs, max_nq, st);
+    if (n_jobs == 0 || max_nq == 0) return hipSuccess;
+    return launch_y_sliced(k_l2_emit_count, a, &L2EmitArgs::job_base, n_jobs, (max_nq + 255) / 256, 256, st);
 }
 
 hipError_t launch_l2_emit(const L2EmitArgs& a, uint32_t n_jobs, uint32_t max_nq, hipStream_t st) {
-    return launch_sliced(k_l2_emit, a, n_jobs, max_nq, st);
+    if (n_jobs == 0 || max_nq == 0) return hipSuccess;
+    return launch_y_sliced(k_l2_emit, a, &L2EmitArgs::job_base, n_jobs, (max_nq + 255) / 256, 256, st);
 }
 
 hipError_t launch_l2_emit_offsets(const uint32_t* blocks, const uint32_t* pair_block, uint64_t* offsets, uint32_t n, hipStream_t st) {

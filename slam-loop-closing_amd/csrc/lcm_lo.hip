@@ -2,7 +2,7 @@
 // hypotheses of every pair are refitted on their own inliers, in rounds under a shrinking threshold, and a refit replaces the
 // RANSAC's record only when it holds strictly more inliers.  Every step is defined in lcm_lo_device.h; the inlier rule, the
 // camera normalisation, the constraint row and the projection are lcm_epi_device.h's.  The kernels run after k_epi_mask on
-// the same records, hypotheses and counts.  The pair comes from blockIdx.y, in slices of grid_y_limit() pairs as k_epi_mask's.
+// the same records, hypotheses and counts.  The pair comes from blockIdx.y, in slices (launch_y_sliced) as k_epi_mask's.
 //
 // k_lo_select   one workgroup of 256 threads per pair: the exact 64 largest of the pair's `iters` keys (count << 16 |
 //               0xFFFF - hypothesis; unique).  Four passes of an 8-bit radix select over the keys (a 256-bin histogram in LDS
@@ -253,24 +253,12 @@ __global__ __launch_bounds__(64) void k_lo_refine(LoArgs a) {
     }
 }
 
-template <typename K>
-static hipError_t launch_sliced(K kernel, const LoArgs& a, uint32_t n_pairs, uint32_t block, hipStream_t st) {
-    if (n_pairs == 0) return hipSuccess;
-    uint32_t lim = 0;
-    hipError_t e = grid_y_limit(&lim);
-    if (e != hipSuccess) return e;
-    LoArgs s = a;                                              // slices of at most gridDim.y's limit (lcm_kernels.h)
-    for (s.pair_base = 0; s.pair_base < n_pairs; s.pair_base += lim) {
-        hipLaunchKernelGGL(kernel, dim3(1, std::min(lim, n_pairs - s.pair_base)), dim3(block), 0, st, s);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        if (n_pairs - s.pair_base <= lim) break;
-    }
-    return hipSuccess;
+hipError_t launch_lo_select(const LoArgs& a, uint32_t n_pairs, hipStream_t st) {
+    return launch_y_sliced(k_lo_select, a, &LoArgs::pair_base, n_pairs, 1, 256, st);
 }
 
-hipError_t launch_lo_select(const LoArgs& a, uint32_t n_pairs, hipStream_t st) { return launch_sliced(k_lo_select, a, n_pairs, 256, st); }
-
-hipError_t launch_lo_refine(const LoArgs& a, uint32_t n_pairs, hipStream_t st) { return launch_sliced(k_lo_refine, a, n_pairs, 64, st); }
+hipError_t launch_lo_refine(const LoArgs& a, uint32_t n_pairs, hipStream_t st) {
+    return launch_y_sliced(k_lo_refine, a, &LoArgs::pair_base, n_pairs, 1, 64, st);
+}
 
 }  // namespace lcm

@@ -3,7 +3,8 @@
 //   lo_threshold2            the inlier threshold of a round: (t * mult)^2
 //   lo_hartley_scale         Hartley's isotropic scale from a side's summed squared distances to its mean
 //   lo_add_moments           one record's constraint row r (epi_put_row's layout) added to the 45 sums of r r^T
-//   lo_eig9                  the eigenvector of the smallest eigenvalue of the 9 x 9 moment matrix: cyclic Jacobi, fixed sweeps
+//   lo_eig9                  the eigenvector of the smallest eigenvalue of the 9 x 9 moment matrix: cyclic Jacobi, fixed sweeps,
+//                            the packed index and the rotation's angle lcm_geom_device.h's
 //   lo_denormalise           F = T2^T mat(f) T1
 //   lo_accepts / lo_lane_key the acceptance rule of a seed and the key that picks the winning seed of a pair
 // The inlier rule, the camera normalisation, the constraint row and the projection are lcm_epi_device.h's: called, not restated.
@@ -14,6 +15,7 @@
 #include <stdint.h>
 
 #include "lcm_epi_device.h"
+#include "lcm_geom_device.h"
 
 namespace lcm {
 
@@ -79,12 +81,6 @@ __host__ __device__ __forceinline__ void lo_add_moments(double (&m)[LO_MOMENTS],
         }
 }
 
-// position of element (i, j) of the symmetric matrix in the packed upper triangle
-__host__ __device__ __forceinline__ int lo_sym(int i, int j) {
-    const int lo = i < j ? i : j, hi = i < j ? j : i;
-    return lo * 9 - lo * (lo - 1) / 2 + (hi - lo);
-}
-
 // Eigenvector of the smallest eigenvalue of the symmetric matrix packed in W[k * STRIDE], k < 45 (destroyed): cyclic Jacobi,
 // LO_JACOBI_SWEEPS sweeps over the 36 pairs (p, q); the product of the rotations accumulates in W[(45 + 9 i + j) * STRIDE].
 // STRIDE = 64 on the device: a lane-private column of LDS, so the runtime indices cost nothing and no lane meets another's
@@ -102,25 +98,23 @@ __host__ __device__ __forceinline__ void lo_eig9(double* W, double (&f)[9]) {
         for (int p = 0; p < 8; ++p)
 #pragma clang loop unroll(disable)
             for (int q = p + 1; q < 9; ++q) {
-                const int pp = lo_sym(p, p), qq = lo_sym(q, q), pq = lo_sym(p, q);
+                const int pp = sym_index<9>(p, p), qq = sym_index<9>(q, q), pq = sym_index<9>(p, q);
                 const double app = W[pp * STRIDE], aqq = W[qq * STRIDE], apq = W[pq * STRIDE];
                 // both rows and both columns are read before the angle is known: their LDS latency hides behind its
                 // division and square roots, and no store stands between two loads
                 double ap[9], aq[9], vp[9], vq[9];
 #pragma unroll
                 for (int k = 0; k < 9; ++k) {
-                    ap[k] = W[lo_sym(k, p) * STRIDE]; aq[k] = W[lo_sym(k, q) * STRIDE];
+                    ap[k] = W[sym_index<9>(k, p) * STRIDE]; aq[k] = W[sym_index<9>(k, q) * STRIDE];
                     vp[k] = V[(9 * k + p) * STRIDE]; vq[k] = V[(9 * k + q) * STRIDE];
                 }
-                if (!(apq != 0.0 && apq * apq > 1e-36 * fabs(app * aqq))) continue;
-                const double zeta = (aqq - app) / (2.0 * apq);
-                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
+                double t, cs, sn;
+                if (!jacobi_angle(app, aqq, apq, t, cs, sn)) continue;
 #pragma unroll
                 for (int k = 0; k < 9; ++k) {
                     if (k != p && k != q) {
-                        W[lo_sym(k, p) * STRIDE] = cs * ap[k] - sn * aq[k];
-                        W[lo_sym(k, q) * STRIDE] = sn * ap[k] + cs * aq[k];
+                        W[sym_index<9>(k, p) * STRIDE] = cs * ap[k] - sn * aq[k];
+                        W[sym_index<9>(k, q) * STRIDE] = sn * ap[k] + cs * aq[k];
                     }
                     V[(9 * k + p) * STRIDE] = cs * vp[k] - sn * vq[k];
                     V[(9 * k + q) * STRIDE] = sn * vp[k] + cs * vq[k];
@@ -130,9 +124,9 @@ __host__ __device__ __forceinline__ void lo_eig9(double* W, double (&f)[9]) {
                 W[pq * STRIDE] = 0.0;
             }
     int col = 0;
-    double least = W[lo_sym(0, 0) * STRIDE];
+    double least = W[sym_index<9>(0, 0) * STRIDE];
     for (int k = 1; k < 9; ++k) {
-        const double dk = W[lo_sym(k, k) * STRIDE];
+        const double dk = W[sym_index<9>(k, k) * STRIDE];
         if (dk < least) { least = dk; col = k; }
     }
 #pragma unroll

@@ -11,9 +11,6 @@
 
 static_assert(sizeof(lcm_map_params) == 112 && sizeof(lcm_map_tri) == 64 && sizeof(lcm::MapTri) == 64 && sizeof(lcm_map_pair_info) == 48 &&
               sizeof(lcm_map_keyframe_report) == 168 && sizeof(lcm::MapPair) == 448, "record sizes");
-static_assert(sizeof(lcm::MapPoint) == sizeof(lcm_ba_point) && sizeof(lcm::MapObs) == sizeof(lcm_ba_obs) && offsetof(lcm::MapObs, point) == 4 &&
-              offsetof(lcm_ba_obs, point) == 4 && offsetof(lcm::MapObs, u) == 8 && offsetof(lcm_ba_obs, u) == 8 &&
-              offsetof(lcm::MapObs, v) == 16 && offsetof(lcm_ba_obs, v) == 16, "the map's records are the bundle adjustment's");
 static_assert(offsetof(lcm_map_tri, depth1) == 24 && offsetof(lcm::MapTri, depth1) == 24 && offsetof(lcm_map_tri, err2) == 56 &&
               offsetof(lcm::MapTri, err2) == 56 && offsetof(lcm_map_params, min_parallax_deg) == 32 && offsetof(lcm_map_params, min_tracked) == 88 &&
               offsetof(lcm_map_params, reserved) == 100 && offsetof(lcm_map_pair_info, counts) == 16 &&
@@ -43,7 +40,7 @@ int map_tri_enqueue(lcm_handle* h, const uint4* d_pts, const uint64_t* d_off, si
     if (n_pairs == 0) return LCM_OK;
     HIP_TRY(hipMemcpyAsync(s.d_pairs, pairs, n_pairs * sizeof(MapPair), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemsetAsync(s.d_counts, 0, n_pairs * MAP_STATUSES * sizeof(uint32_t), h->stream));
-    const MapTriArgs a{d_pts, d_off, d_mask, s.d_pairs, s.d_tri, s.d_status, s.d_counts, MapCamera{mp.fx, mp.fy, mp.cx, mp.cy},
+    const MapTriArgs a{d_pts, d_off, d_mask, s.d_pairs, s.d_tri, s.d_status, s.d_counts, Camera{mp.fx, mp.fy, mp.cx, mp.cy},
                        MapLimits{mp.min_depth, mp.max_depth, mp.max_reproj}};
     const hipError_t e = launch_map_triangulate(a, (uint32_t)n_pairs, max_n, h->stream);
     return e == hipSuccess ? LCM_OK : fail(LCM_ERR_HIP, "triangulation kernel launch failed: %s", hipGetErrorString(e));
@@ -91,8 +88,8 @@ int map_merge_download(lcm_handle* h, const MapMergeIO& io, int n_new, int n_mer
     auto& s = h->map;
     const size_t n_obs = 2 * (size_t)n_new + (size_t)n_merged;
     if (io.n == 0) return LCM_OK;
-    if (n_new) HIP_TRY(hipMemcpyAsync(io.points_out, s.d_points, (size_t)n_new * sizeof(MapPoint), hipMemcpyDeviceToHost, h->stream));
-    if (n_obs) HIP_TRY(hipMemcpyAsync(io.obs_out, s.d_obs, n_obs * sizeof(MapObs), hipMemcpyDeviceToHost, h->stream));
+    if (n_new) HIP_TRY(hipMemcpyAsync(io.points_out, s.d_points, (size_t)n_new * sizeof(Point3), hipMemcpyDeviceToHost, h->stream));
+    if (n_obs) HIP_TRY(hipMemcpyAsync(io.obs_out, s.d_obs, n_obs * sizeof(Observation), hipMemcpyDeviceToHost, h->stream));
     if (io.status_out) HIP_TRY(hipMemcpyAsync(io.status_out, s.d_status_out, io.n, hipMemcpyDeviceToHost, h->stream));
     if (io.n_kp1) HIP_TRY(hipMemcpyAsync(io.table1, s.d_tab, (size_t)io.n_kp1 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     if (io.n_kp2) HIP_TRY(hipMemcpyAsync(io.table2, s.d_tab + io.n_kp1, (size_t)io.n_kp2 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));

@@ -1,9 +1,9 @@
 // lcm_map.hip — the reference's map building before the loop (src/main.cpp:1152-1351) on the device: the median displacement of the
 // keyframe gate (:171-189), cv::triangulatePoints with the depth, parallax and reprojection filters (:1250-1313) and the merge of a
-// keyframe's points into the map (:1315-1340), with every step's arithmetic defined in lcm_map_device.h.  The loop over the matches
-// looks sequential but is a filter per record, an ordered compaction and a last-writer scatter: a knnMatch list holds every
-// query_idx once.  No floating-point atomic anywhere: the integer atomics below count or take a maximum, which no order changes, so
-// the same call gives the same bytes.
+// keyframe's points into the map (:1315-1340), with every step's arithmetic defined in lcm_map_device.h (the shared part in
+// lcm_geom_device.h).  The loop over the matches looks sequential but is a filter per record, an ordered compaction and a
+// last-writer scatter: a knnMatch list holds every query_idx once.  No floating-point atomic anywhere: the integer atomics below
+// count or take a maximum, which no order changes, so the same call gives the same bytes.
 //
 // k_map_median       one workgroup of 256 threads per pair: the exact element n / 2 of the pair's sorted displacements by a radix
 //                    select over the doubles' 64-bit patterns (non-negative doubles order as their patterns do): eight passes of
@@ -145,13 +145,13 @@ __global__ __launch_bounds__(256) void k_map_merge_emit(MapMergeArgs a) {
     if (is_new) {
         point = a.n_points + (int32_t)r_new;
         const MapTri t = a.tri[i];
-        a.points_out[r_new] = MapPoint{t.X[0], t.X[1], t.X[2]};
-        a.obs_out[at++] = MapObs{a.kf1, point, qx, qy};
+        a.points_out[r_new] = Point3{t.X[0], t.X[1], t.X[2]};
+        a.obs_out[at++] = Observation{a.kf1, point, qx, qy};
         a.table1[mt.x] = point;
     } else {
         point = a.table1[mt.x];
     }
-    a.obs_out[at] = MapObs{a.kf2, point, tx, ty};
+    a.obs_out[at] = Observation{a.kf2, point, tx, ty};
     if (a.winner[mt.y] == (int32_t)i) a.table2[mt.y] = point;
     a.status_out[i] = (uint8_t)(is_new ? MAP_NEW : MAP_MERGED);
 }

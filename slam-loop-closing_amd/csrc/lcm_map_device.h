@@ -5,10 +5,10 @@
 //   map_system            the ten sums of M = A^T A of cv::triangulatePoints' 4 x 4 system
 //   map_rotate            one Jacobi rotation of the packed 4 x 4 matrix and of the rotations' product
 //   map_jacobi4           the eigenvector of M's smallest eigenvalue: cyclic Jacobi, fixed sweeps, everything in registers
-//   map_camera_point      Xc = (R X) + t
 //   map_parallax_cos      the cosine of the angle between the two rays (:200-222, without the acos)
 //   map_reproj_error      computeSingleReprojError (:227-246)
 //   map_record            one record from its four floats to its status and its lcm_map_tri, in the reference's order (:1261-1313)
+// The camera point, the projection, the packed index and the rotation's angle are lcm_geom_device.h's: called, not restated.
 // In double, every product and sum rounded on its own (fp contract off), sums left to right.  Every index into M and into the
 // rotations' product is a compile-time constant (the pairs (p, q) and the rows are template arguments), so the 26 doubles live in
 // registers and the kernel needs no scratch memory.  Everything is __host__ __device__: the host compiles the same text
@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+
+#include "lcm_geom_device.h"
 
 namespace lcm {
 
@@ -31,14 +33,12 @@ constexpr double MAP_MIN_W = 1e-9;            // :1269
 constexpr double MAP_MIN_RAY = 1e-9;          // :213
 constexpr double MAP_BEHIND = 1e9;            // :237
 
-// The device's records = lcm_map_tri, lcm_ba_point, lcm_ba_obs (include/lcm.h; lcm_map.cpp asserts the layouts)
+// The device's record = lcm_map_tri (include/lcm.h; lcm_map.cpp asserts the layout); a merge writes lcm_geom_device.h's Point3 and
+// Observation
 struct MapTri { double X[3]; double depth1, depth2, cos_parallax, err1, err2; };
-struct MapPoint { double x, y, z; };
-struct MapObs { int32_t cam, point; double u, v; };
 // One pair as the host planner leaves it (lcm_map_host.h, map_plan_pair): the two 3 x 4 matrices K [R | t] row-major, the poses,
 // the centres, the baseline and the cosine of the smallest parallax
 struct MapPair { double P1[12], P2[12], R1[9], t1[3], R2[9], t2[3], C1[3], C2[3], baseline, cos_min; };
-struct MapCamera { double fx, fy, cx, cy; };
 struct MapLimits { double min_depth, max_depth, max_reproj; };
 
 // dx = (double)(tx - qx) with the subtraction in float, dy likewise; sqrt(dx dx + dy dy)
@@ -49,12 +49,7 @@ __host__ __device__ __forceinline__ double map_displacement(float qx, float qy, 
     return sqrt(dx * dx + dy * dy);
 }
 
-// position of element (i, j) of the symmetric 4 x 4 matrix in the packed upper triangle, row-major
-__host__ __device__ constexpr int map_sym(int i, int j) {
-    return (i < j ? i : j) * 4 - (i < j ? i : j) * ((i < j ? i : j) - 1) / 2 + ((i < j ? j : i) - (i < j ? i : j));
-}
-
-// The rows of A: x1 P1[2] - P1[0], y1 P1[2] - P1[1], x2 P2[2] - P2[0], y2 P2[2] - P2[1]; m[map_sym(i, j)] = the sum over the
+// The rows of A: x1 P1[2] - P1[0], y1 P1[2] - P1[1], x2 P2[2] - P2[0], y2 P2[2] - P2[1]; m[sym_index<4>(i, j)] = the sum over the
 // four rows, in that order, of A[r][i] A[r][j]
 __host__ __device__ __forceinline__ void map_system(const double (&P1)[12], const double (&P2)[12], double x1, double y1, double x2, double y2,
                                                     double (&m)[10]) {
@@ -74,7 +69,7 @@ __host__ __device__ __forceinline__ void map_system(const double (&P1)[12], cons
             double s = A[0][i] * A[0][j];
 #pragma unroll
             for (int r = 1; r < 4; ++r) s = s + A[r][i] * A[r][j];
-            m[map_sym(i, j)] = s;
+            m[sym_index<4>(i, j)] = s;
         }
 }
 
@@ -83,32 +78,29 @@ template <int K, int P, int Q>
 __host__ __device__ __forceinline__ void map_rotate_row(double (&a)[10], double (&v)[16], double cs, double sn) {
 #pragma clang fp contract(off)
     if (K != P && K != Q) {
-        const double akp = a[map_sym(K, P)], akq = a[map_sym(K, Q)];
-        a[map_sym(K, P)] = cs * akp - sn * akq;
-        a[map_sym(K, Q)] = sn * akp + cs * akq;
+        const double akp = a[sym_index<4>(K, P)], akq = a[sym_index<4>(K, Q)];
+        a[sym_index<4>(K, P)] = cs * akp - sn * akq;
+        a[sym_index<4>(K, Q)] = sn * akp + cs * akq;
     }
     const double vkp = v[4 * K + P], vkq = v[4 * K + Q];
     v[4 * K + P] = cs * vkp - sn * vkq;
     v[4 * K + Q] = sn * vkp + cs * vkq;
 }
 
-// The local optimisation's rotation (lcm_lo_device.h, lo_eig9) on the pair (P, Q): skipped where the off-diagonal entry is zero
-// or below 1e-18 of the geometric mean of the two diagonal entries
+// One rotation on the pair (P, Q), skipped where jacobi_angle says so
 template <int P, int Q>
 __host__ __device__ __forceinline__ void map_rotate(double (&a)[10], double (&v)[16]) {
 #pragma clang fp contract(off)
-    const double app = a[map_sym(P, P)], aqq = a[map_sym(Q, Q)], apq = a[map_sym(P, Q)];
-    if (!(apq != 0.0 && apq * apq > 1e-36 * fabs(app * aqq))) return;
-    const double zeta = (aqq - app) / (2.0 * apq);
-    const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-    const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
+    const double app = a[sym_index<4>(P, P)], aqq = a[sym_index<4>(Q, Q)], apq = a[sym_index<4>(P, Q)];
+    double t, cs, sn;
+    if (!jacobi_angle(app, aqq, apq, t, cs, sn)) return;
     map_rotate_row<0, P, Q>(a, v, cs, sn);
     map_rotate_row<1, P, Q>(a, v, cs, sn);
     map_rotate_row<2, P, Q>(a, v, cs, sn);
     map_rotate_row<3, P, Q>(a, v, cs, sn);
-    a[map_sym(P, P)] = app - t * apq;
-    a[map_sym(Q, Q)] = aqq + t * apq;
-    a[map_sym(P, Q)] = 0.0;
+    a[sym_index<4>(P, P)] = app - t * apq;
+    a[sym_index<4>(Q, Q)] = aqq + t * apq;
+    a[sym_index<4>(P, Q)] = 0.0;
 }
 
 // Eigenvector of the smallest eigenvalue of the packed symmetric matrix m (destroyed): MAP_JACOBI_SWEEPS sweeps over the six
@@ -121,18 +113,11 @@ __host__ __device__ __forceinline__ void map_jacobi4(double (&m)[10], double (&h
         map_rotate<0, 1>(m, v); map_rotate<0, 2>(m, v); map_rotate<0, 3>(m, v);
         map_rotate<1, 2>(m, v); map_rotate<1, 3>(m, v); map_rotate<2, 3>(m, v);
     }
-    double least = m[map_sym(0, 0)];
+    double least = m[sym_index<4>(0, 0)];
     h[0] = v[0]; h[1] = v[4]; h[2] = v[8]; h[3] = v[12];
-    if (m[map_sym(1, 1)] < least) { least = m[map_sym(1, 1)]; h[0] = v[1]; h[1] = v[5]; h[2] = v[9]; h[3] = v[13]; }
-    if (m[map_sym(2, 2)] < least) { least = m[map_sym(2, 2)]; h[0] = v[2]; h[1] = v[6]; h[2] = v[10]; h[3] = v[14]; }
-    if (m[map_sym(3, 3)] < least) { least = m[map_sym(3, 3)]; h[0] = v[3]; h[1] = v[7]; h[2] = v[11]; h[3] = v[15]; }
-}
-
-// Xc = (R X) + t, each row of the product summed left to right
-__host__ __device__ __forceinline__ void map_camera_point(const double (&R)[9], const double (&t)[3], const double (&X)[3], double (&Xc)[3]) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int i = 0; i < 3; ++i) Xc[i] = (R[3 * i] * X[0] + R[3 * i + 1] * X[1] + R[3 * i + 2] * X[2]) + t[i];
+    if (m[sym_index<4>(1, 1)] < least) { least = m[sym_index<4>(1, 1)]; h[0] = v[1]; h[1] = v[5]; h[2] = v[9]; h[3] = v[13]; }
+    if (m[sym_index<4>(2, 2)] < least) { least = m[sym_index<4>(2, 2)]; h[0] = v[2]; h[1] = v[6]; h[2] = v[10]; h[3] = v[14]; }
+    if (m[sym_index<4>(3, 3)] < least) { least = m[sym_index<4>(3, 3)]; h[0] = v[3]; h[1] = v[7]; h[2] = v[11]; h[3] = v[15]; }
 }
 
 // The rays X - C_i; a norm below 1e-9 is parallax 0 (cosine 1); else the dot product of the normalised rays clamped to [-1, 1]
@@ -146,17 +131,18 @@ __host__ __device__ __forceinline__ double map_parallax_cos(const double (&C1)[3
     return c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);
 }
 
-// 1e9 at z <= 0; else u = ((fx x) / z) + cx, v = ((fy y) / z) + cy and the distance to the pixel
-__host__ __device__ __forceinline__ double map_reproj_error(const MapCamera& K, const double (&Xc)[3], double px, double py) {
+// 1e9 at z <= 0; else the distance from the projection to the pixel
+__host__ __device__ __forceinline__ double map_reproj_error(const Camera& K, const double (&Xc)[3], double px, double py) {
 #pragma clang fp contract(off)
     if (Xc[2] <= 0.0) return MAP_BEHIND;
-    const double u = ((K.fx * Xc[0]) / Xc[2]) + K.cx, v = ((K.fy * Xc[1]) / Xc[2]) + K.cy;
+    double u, v;
+    pinhole_project(K, Xc, u, v);
     const double dx = u - px, dy = v - py;
     return sqrt(dx * dx + dy * dy);
 }
 
 // One record that takes part: its lcm_map_tri (all zero without a point) and its status
-__host__ __device__ __forceinline__ int map_record(const MapPair& pr, const MapCamera& K, const MapLimits& lim, float qx, float qy, float tx,
+__host__ __device__ __forceinline__ int map_record(const MapPair& pr, const Camera& K, const MapLimits& lim, float qx, float qy, float tx,
                                                    float ty, MapTri& out) {
 #pragma clang fp contract(off)
     const double x1 = (double)qx, y1 = (double)qy, x2 = (double)tx, y2 = (double)ty;
@@ -167,8 +153,8 @@ __host__ __device__ __forceinline__ int map_record(const MapPair& pr, const MapC
     if (fabs(h[3]) < MAP_MIN_W) return MAP_NO_POINT;
     const double X[3] = {h[0] / h[3], h[1] / h[3], h[2] / h[3]};
     double Xc1[3], Xc2[3];
-    map_camera_point(pr.R1, pr.t1, X, Xc1);
-    map_camera_point(pr.R2, pr.t2, X, Xc2);
+    rigid_apply(pr.R1, pr.t1, X, Xc1);
+    rigid_apply(pr.R2, pr.t2, X, Xc2);
     out.X[0] = X[0]; out.X[1] = X[1]; out.X[2] = X[2];
     out.depth1 = Xc1[2]; out.depth2 = Xc2[2];
     out.cos_parallax = map_parallax_cos(pr.C1, pr.C2, X);
@@ -189,14 +175,14 @@ struct MapTriArgs {
     const MapPair* pairs;
     MapTri* tri; uint8_t* status;
     uint32_t* counts;            // MAP_STATUSES words per pair, zeroed by the caller: integer sums, the same whatever the order
-    MapCamera K; MapLimits lim;
+    Camera K; MapLimits lim;
 };
 struct MapMergeArgs {
     const uint4* matches; const uint4* pts; const MapTri* tri; const uint8_t* status;
     int32_t* table1; int32_t* table2;
     int32_t* winner;             // per keypoint of view 2: the largest index of an accepted record that names it, -1 = none
     uint32_t* blk_accepted; uint32_t* blk_new;     // per block of MAP_THREADS records; after the scans their exclusive prefixes
-    MapPoint* points_out; MapObs* obs_out; uint8_t* status_out;
+    Point3* points_out; Observation* obs_out; uint8_t* status_out;
     uint32_t n; int32_t kf1, kf2, n_points;
 };
 hipError_t launch_map_median(const MapMedianArgs& a, uint32_t n_pairs, hipStream_t st);                     // k_map_median

@@ -6,9 +6,9 @@
 
 #include "lcm_pgo_host.h"
 
-static_assert(sizeof(lcm_pgo_pose) == 96 && sizeof(lcm::PgoPose) == 96 && sizeof(lcm_pgo_edge) == 112 && sizeof(lcm::PgoEdge) == 112 &&
+static_assert(sizeof(lcm_pgo_pose) == 96 && sizeof(lcm::Pose) == 96 && sizeof(lcm_pgo_edge) == 112 && sizeof(lcm::PgoEdge) == 112 &&
               sizeof(lcm_pgo_params) == 64 && sizeof(lcm_pgo_info) == 48, "record sizes");
-static_assert(offsetof(lcm_pgo_pose, t) == 72 && offsetof(lcm::PgoPose, t) == 72 && offsetof(lcm_pgo_edge, t) == 72 &&
+static_assert(offsetof(lcm_pgo_pose, t) == 72 && offsetof(lcm::Pose, t) == 72 && offsetof(lcm_pgo_edge, t) == 72 &&
               offsetof(lcm::PgoEdge, t) == 72 && offsetof(lcm_pgo_edge, weight) == 96 && offsetof(lcm::PgoEdge, weight) == 96 &&
               offsetof(lcm_pgo_edge, from) == 104 && offsetof(lcm::PgoEdge, from) == 104 && offsetof(lcm_pgo_edge, to) == 108 &&
               offsetof(lcm::PgoEdge, to) == 108, "record layout");
@@ -22,8 +22,6 @@ static_assert(offsetof(lcm::PgoState, lambda) == 24 && offsetof(lcm::PgoState, i
 namespace {
 
 struct PgoSeam { double* params; double* res; double* jac; double* dp; };      // lcm_pgo_step's outputs
-
-size_t up16(size_t v) { return (v + 15) / 16 * 16; }
 
 // One run: `iters` iterations enqueued over the staged graph.  seam == NULL: lcm_pgo_optimize (poses_out), else lcm_pgo_step.
 int pgo_run(lcm_handle* h, const lcm_pgo_pose* poses, const uint8_t* valid, int n_poses, const lcm_pgo_edge* edges, int n_edges,
@@ -65,9 +63,9 @@ int pgo_run(lcm_handle* h, const lcm_pgo_pose* poses, const uint8_t* valid, int 
     HIP_TRY(hipMemsetAsync(w + off[14], 0, sizes[14] * sizeof(double), h->stream));
 
     lcm::PgoArgs a{};
-    a.poses = reinterpret_cast<const lcm::PgoPose*>(s.d_in); a.edges = reinterpret_cast<const lcm::PgoEdge*>(s.d_in + o_edges);
+    a.poses = reinterpret_cast<const lcm::Pose*>(s.d_in); a.edges = reinterpret_cast<const lcm::PgoEdge*>(s.d_in + o_edges);
     a.tab = reinterpret_cast<const int32_t*>(s.d_in + o_tab); a.valid = s.d_in + o_valid;
-    a.poses_out = reinterpret_cast<lcm::PgoPose*>(s.d_in + o_out); a.st = reinterpret_cast<lcm::PgoState*>(s.d_in + o_state);
+    a.poses_out = reinterpret_cast<lcm::Pose*>(s.d_in + o_out); a.st = reinterpret_cast<lcm::PgoState*>(s.d_in + o_state);
     a.params = w + off[0]; a.res = w + off[1]; a.jac = w + off[2]; a.D = w + off[3]; a.C = w + off[4]; a.L = w + off[5]; a.M = w + off[6];
     a.B = w + off[7]; a.W = w + off[8]; a.S = w + off[9]; a.T = w + off[10]; a.g = w + off[11]; a.dpu = w + off[12]; a.tr = w + off[13];
     a.dp_out = w + off[14];

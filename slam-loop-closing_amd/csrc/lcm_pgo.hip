@@ -1,8 +1,9 @@
 // lcm_pgo.hip — the reference's optimizePoseGraph (src/main.cpp:282-445) on the device, with every step's arithmetic defined in
-// lcm_pgo_device.h: the block-sparse central-difference linearisation, the normal equations in the plan's order (interior poses,
-// then the border: lcm_pgo_host.h) and an exact block Cholesky of them.  No floating-point atomic anywhere: every sum has one
-// owner and a fixed order, so the same call gives the same bytes.  The convergence decision stays on the device: the host
-// enqueues the iterations back to back, and a kernel that finds PgoState::done set returns at once.
+// lcm_pgo_device.h and, where other stages share it, lcm_geom_device.h: the block-sparse central-difference linearisation, the
+// normal equations in the plan's order (interior poses, then the border: lcm_pgo_host.h) and an exact block Cholesky of them.
+// No floating-point atomic anywhere: every sum has one owner and a fixed order, so the same call gives the same bytes.  The
+// convergence decision stays on the device: the host enqueues the iterations back to back, and a kernel that finds
+// PgoState::done set returns at once.
 //
 // k_pgo_params     one thread per pose, once per run: the parameters (log R, t) of every valid pose; zeros for an invalid one.
 // k_pgo_linearise  16 lanes per edge, four edges per wave, 256 threads per workgroup, the grid over the edges.  Lanes 0 .. 11 own
@@ -55,7 +56,7 @@ __device__ __forceinline__ void pgo_pose_at(const PgoArgs& a, uint32_t idx, int 
         r[j] = (j == k) ? p[j] + delta : p[j];
         t[j] = (j + 3 == k) ? p[j + 3] + delta : p[j + 3];
     }
-    pgo_exp(r, R);
+    so3_exp(r, R);
 }
 
 }  // namespace
@@ -72,7 +73,7 @@ __global__ __launch_bounds__(256) void k_pgo_params(PgoArgs a) {
     double R[9], r[3];
 #pragma unroll
     for (int k = 0; k < 9; ++k) R[k] = a.poses[p].R[k];
-    if (!pgo_log(R, r) && p != 0) a.st->half_turn = 1;
+    if (!so3_log(R, r) && p != 0) a.st->half_turn = 1;
 #pragma unroll
     for (int k = 0; k < 3; ++k) { out[k] = r[k]; out[3 + k] = a.poses[p].t[k]; }
 }
@@ -220,7 +221,7 @@ __global__ __launch_bounds__(128) void k_pgo_sweep(PgoArgs a) {
                 double x[6];
 #pragma unroll
                 for (int j = 0; j < 6; ++j) x[j] = Cp[6 * j + r];
-                pgo_lower_solve6(Lp, x);
+                lower_solve<6>(Lp, x);
 #pragma unroll
                 for (int j = 0; j < 6; ++j) M[6 * r + j] = x[j];
             }
@@ -235,9 +236,9 @@ __global__ __launch_bounds__(128) void k_pgo_sweep(PgoArgs a) {
                 double s = (r == cc) ? Di[6 * r + cc] + lambda : Di[6 * r + cc];
 #pragma unroll
                 for (int k = 0; k < 6; ++k) s = s - M[6 * r + k] * M[6 * cc + k];
-                Lc[pgo_tri(r, cc)] = s;
+                Lc[tri_index(r, cc)] = s;
             }
-        ok = pgo_chol6(Lc);
+        ok = chol<6>(Lc);
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
             double s = 0.0;
@@ -246,7 +247,7 @@ __global__ __launch_bounds__(128) void k_pgo_sweep(PgoArgs a) {
             for (int j = 0; j < 6; ++j) s = s - M[6 * k + j] * wp[j];
             w[k] = s;
         }
-        pgo_lower_solve6(Lc, w);
+        lower_solve<6>(Lc, w);
         if (active && ok) {
 #pragma unroll
             for (int k = 0; k < 6; ++k) a.W[((size_t)i * 6 + k) * ncols + tid] = w[k];
@@ -348,7 +349,7 @@ __global__ __launch_bounds__(256) void k_pgo_finish(PgoArgs a) {
             }
 #pragma unroll
             for (int k = 0; k < 21; ++k) Lc[k] = a.L[36 * (size_t)i + k];
-            pgo_upper_solve6(Lc, x);
+            upper_solve<6>(Lc, x);
             if (tid == 0) {
 #pragma unroll
                 for (int k = 0; k < 6; ++k) a.dpu[6 * (size_t)i + k] = x[k];
@@ -383,11 +384,11 @@ __global__ __launch_bounds__(256) void k_pgo_writeback(PgoArgs a) {
     const uint32_t p = blockIdx.x * 256 + threadIdx.x;
     if (p >= a.n_poses) return;
     const bool untouched = a.st->status == 3 && a.st->iterations == 0;
-    PgoPose out = a.poses[p];
+    Pose out = a.poses[p];
     if (p != 0 && a.valid[p] && !untouched) {
         const double* q = a.params + 6 * (size_t)p;
         const double r[3] = {q[0], q[1], q[2]};
-        pgo_exp(r, out.R);
+        so3_exp(r, out.R);
 #pragma unroll
         for (int k = 0; k < 3; ++k) out.t[k] = q[3 + k];
     }

@@ -193,8 +193,8 @@ inline int pgo_build_graph(const lcm_pgo_pose* poses, const uint8_t* valid, int 
             std::memset(&e, 0, sizeof(e));
             double Ra[9], Rb[9], ta[3], rt[3];
             std::memcpy(Ra, poses[i - 1].R, sizeof(Ra)); std::memcpy(Rb, poses[i].R, sizeof(Rb)); std::memcpy(ta, poses[i - 1].t, sizeof(ta));
-            pgo_mul_nt(Rb, Ra, e.R);
-            pgo_apply(e.R, ta, rt);
+            mat3_mul_nt(Rb, Ra, e.R);
+            mat3_apply(e.R, ta, rt);
             for (int k = 0; k < 3; ++k) e.t[k] = poses[i].t[k] - rt[k];
             e.weight = 1.0; e.from = i - 1; e.to = i;
         }
@@ -213,9 +213,9 @@ inline int pgo_build_graph(const lcm_pgo_pose* poses, const uint8_t* valid, int 
 inline bool pgo_loop_error(const lcm_pgo_pose* poses, int past, int curr, const double* R_loop, double (&rvec)[3]) {
     double Rp[9], Rc[9], Rl[9], Rseq[9], Rerr[9];
     std::memcpy(Rp, poses[past].R, sizeof(Rp)); std::memcpy(Rc, poses[curr].R, sizeof(Rc)); std::memcpy(Rl, R_loop, sizeof(Rl));
-    pgo_mul_nt(Rc, Rp, Rseq);
-    pgo_mul_nt(Rl, Rseq, Rerr);
-    return pgo_log(Rerr, rvec);
+    mat3_mul_nt(Rc, Rp, Rseq);
+    mat3_mul_nt(Rl, Rseq, Rerr);
+    return so3_log(Rerr, rvec);
 }
 
 inline double pgo_rotation_drift(const lcm_pgo_pose* poses, int past, int curr, const double* R_loop) {
@@ -224,8 +224,8 @@ inline double pgo_rotation_drift(const lcm_pgo_pose* poses, int past, int curr, 
     if (pgo_loop_error(poses, past, curr, R_loop, rv)) return std::sqrt(rv[0] * rv[0] + rv[1] * rv[1] + rv[2] * rv[2]);
     double Rp[9], Rc[9], Rl[9], Rseq[9], Rerr[9];      // half a turn: rv is v, the angle atan2(|v|, c)
     std::memcpy(Rp, poses[past].R, sizeof(Rp)); std::memcpy(Rc, poses[curr].R, sizeof(Rc)); std::memcpy(Rl, R_loop, sizeof(Rl));
-    pgo_mul_nt(Rc, Rp, Rseq);
-    pgo_mul_nt(Rl, Rseq, Rerr);
+    mat3_mul_nt(Rc, Rp, Rseq);
+    mat3_mul_nt(Rl, Rseq, Rerr);
     double c = 0.5 * (Rerr[0] + Rerr[4] + Rerr[8] - 1.0);
     c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);
     return std::atan2(std::sqrt(rv[0] * rv[0] + rv[1] * rv[1] + rv[2] * rv[2]), c);
@@ -244,9 +244,9 @@ inline bool pgo_linear_correct(const lcm_pgo_pose* poses, const uint8_t* valid, 
         const double alpha = (double)(f - past) / span;
         const double ra[3] = {alpha * rv[0], alpha * rv[1], alpha * rv[2]};
         double Rc[9], Rf[9], Rn[9];
-        pgo_exp(ra, Rc);
+        so3_exp(ra, Rc);
         std::memcpy(Rf, out[f].R, sizeof(Rf));
-        pgo_mul(Rc, Rf, Rn);
+        mat3_mul(Rc, Rf, Rn);
         std::memcpy(out[f].R, Rn, sizeof(Rn));
     }
     return true;

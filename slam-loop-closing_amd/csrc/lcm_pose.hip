@@ -2,7 +2,7 @@
 // the device, with every step defined in lcm_pose_device.h: the closed-form decomposition of E into two rotations and a unit
 // translation, the division-free depth test, and the selection among the four (R, t).  It runs on the point records, the
 // matrices and the inlier mask k_epi_mask has just written (lcm_pose_db_*), or on a caller's (lcm_pose_recover_pairs).
-// The pair comes from blockIdx.y, in slices of grid_y_limit() pairs as k_epi_mask's does.
+// The pair comes from blockIdx.y, in slices (launch_y_sliced, lcm_kernels.h) as k_epi_mask's does.
 //
 // k_pose_recover  one workgroup of 256 threads per pair.  E is read at a wave-uniform address and EVERY thread decomposes
 //                 it (about 150 double operations; the alternative, one lane and a broadcast through LDS behind a barrier,
@@ -117,18 +117,7 @@ __global__ __launch_bounds__(256) void k_pose_recover(PoseArgs a) {
 }
 
 hipError_t launch_pose_recover(const PoseArgs& a, uint32_t n_pairs, hipStream_t st) {
-    if (n_pairs == 0) return hipSuccess;
-    uint32_t lim = 0;
-    hipError_t e = grid_y_limit(&lim);
-    if (e != hipSuccess) return e;
-    PoseArgs s = a;                                            // slices of at most gridDim.y's limit (lcm_kernels.h)
-    for (s.pair_base = 0; s.pair_base < n_pairs; s.pair_base += lim) {
-        hipLaunchKernelGGL(k_pose_recover, dim3(1, std::min(lim, n_pairs - s.pair_base)), dim3(256), 0, st, s);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        if (n_pairs - s.pair_base <= lim) break;
-    }
-    return hipSuccess;
+    return launch_y_sliced(k_pose_recover, a, &PoseArgs::pair_base, n_pairs, 1, 256, st);
 }
 
 }  // namespace lcm

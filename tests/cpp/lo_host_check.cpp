@@ -114,20 +114,20 @@ int main() {
     CHECK(!lcm::lo_hartley_scale(0.0, 0.0, &s));                          // no record selected: 0 / 0
     int seen[lcm::LO_MOMENTS] = {};
     for (int i = 0; i < 9; ++i)
-        for (int j = 0; j < 9; ++j) { CHECK(lcm::lo_sym(i, j) == lcm::lo_sym(j, i)); if (i <= j) ++seen[lcm::lo_sym(i, j)]; }
+        for (int j = 0; j < 9; ++j) { CHECK(lcm::sym_index<9>(i, j) == lcm::sym_index<9>(j, i)); if (i <= j) ++seen[lcm::sym_index<9>(i, j)]; }
     for (int k : seen) CHECK(k == 1);                                     // a bijection onto 0 .. 44
 
     // ---- the eigen step: a diagonal matrix names its smallest entry's axis; a rank-8 projector its null vector
     {
         std::vector<double> W(lcm::LO_WORK, 0.0);
-        for (int k = 0; k < 9; ++k) W[(size_t)lcm::lo_sym(k, k)] = k == 6 ? 0.25 : 1.0 + k;
+        for (int k = 0; k < 9; ++k) W[(size_t)lcm::sym_index<9>(k, k)] = k == 6 ? 0.25 : 1.0 + k;
         double f[9];
         lcm::lo_eig9<1>(W.data(), f);
         for (int k = 0; k < 9; ++k) CHECK(f[k] == (k == 6 ? 1.0 : 0.0));
         double u[9], nu = 0;
         for (int k = 0; k < 9; ++k) { u[k] = 1.0 + 0.37 * k * (k % 2 ? -1 : 1); nu += u[k] * u[k]; }
         for (int i = 0; i < 9; ++i)
-            for (int j = i; j < 9; ++j) W[(size_t)lcm::lo_sym(i, j)] = 3.0 * ((i == j ? 1.0 : 0.0) - u[i] * u[j] / nu);
+            for (int j = i; j < 9; ++j) W[(size_t)lcm::sym_index<9>(i, j)] = 3.0 * ((i == j ? 1.0 : 0.0) - u[i] * u[j] / nu);
         lcm::lo_eig9<1>(W.data(), f);
         double dot = 0, nf = 0;
         for (int k = 0; k < 9; ++k) { dot += f[k] * u[k] / std::sqrt(nu); nf += f[k] * f[k]; }

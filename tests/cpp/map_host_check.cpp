@@ -12,10 +12,10 @@ static int failures = 0;
 #define CHECK(cond) do { if (!(cond)) { std::printf("FAILED line %d: %s\n", __LINE__, #cond); ++failures; } } while (0)
 
 static_assert(sizeof(lcm::MapTri) == sizeof(lcm_map_tri) && sizeof(lcm_map_tri) == 64, "tri");
-static_assert(sizeof(lcm::MapPoint) == sizeof(lcm_ba_point) && sizeof(lcm::MapObs) == sizeof(lcm_ba_obs), "map records");
+static_assert(sizeof(lcm::Point3) == sizeof(lcm_ba_point) && sizeof(lcm::Observation) == sizeof(lcm_ba_obs), "map records");
 static_assert(sizeof(lcm_map_params) == 112 && sizeof(lcm_map_pair_info) == 48 && sizeof(lcm_map_keyframe_report) == 168 && sizeof(lcm::MapPair) == 448, "records");
-static_assert(lcm::map_sym(0, 0) == 0 && lcm::map_sym(0, 3) == 3 && lcm::map_sym(1, 1) == 4 && lcm::map_sym(3, 1) == 6 && lcm::map_sym(2, 2) == 7 &&
-              lcm::map_sym(2, 3) == 8 && lcm::map_sym(3, 3) == 9, "packed upper triangle");
+static_assert(lcm::sym_index<4>(0, 0) == 0 && lcm::sym_index<4>(0, 3) == 3 && lcm::sym_index<4>(1, 1) == 4 && lcm::sym_index<4>(3, 1) == 6 && lcm::sym_index<4>(2, 2) == 7 &&
+              lcm::sym_index<4>(2, 3) == 8 && lcm::sym_index<4>(3, 3) == 9, "packed upper triangle");
 
 static const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
 
@@ -93,7 +93,7 @@ static void check_plan_and_record() {
     CHECK(pr.baseline == 1.0 && pr.C1[0] == 0.0 && pr.C2[0] == 1.0 && pr.C2[1] == 0.0 && pr.cos_min == lcm::map_cos_min(1.0));
     CHECK(pr.P1[0] == 1000.0 && pr.P1[2] == 640.0 && pr.P1[3] == 0.0 && pr.P1[5] == 1000.0 && pr.P1[6] == 360.0 && pr.P1[10] == 1.0);
     CHECK(pr.P2[3] == -1000.0 && pr.P2[7] == 0.0 && pr.P2[11] == 0.0 && pr.t2[0] == -1.0 && pr.R2[4] == 1.0);
-    const lcm::MapCamera K{mp.fx, mp.fy, mp.cx, mp.cy};
+    const lcm::Camera K{mp.fx, mp.fy, mp.cx, mp.cy};
     const lcm::MapLimits lim{mp.min_depth, mp.max_depth, mp.max_reproj};
     lcm::MapTri t;
     // the point (0.5, 0.25, 5): pixels 740, 410 and 540, 410, all floats

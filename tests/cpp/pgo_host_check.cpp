@@ -1,5 +1,5 @@
 // The pure host side of the pose-graph correction (csrc/lcm_pgo_host.h: parameter and input checks, the plan of one graph, the
-// host-only calls) and the arithmetic of csrc/lcm_pgo_device.h compiled for the host, as a stand-alone program:
+// host-only calls) and the edge residual of csrc/lcm_pgo_device.h compiled for the host, as a stand-alone program:
 // tests/test_pgo_abi_host.py builds it with -fsanitize=address,undefined and runs it on the CPU.  No device.  Whole plans are
 // compared with literals for the graph shapes of tests/test_gpu_pgo.py.  Exit status 0 = every check held.
 #include <cstdio>
@@ -12,7 +12,7 @@
 static int failures = 0;
 #define CHECK(cond) do { if (!(cond)) { std::printf("FAILED line %d: %s\n", __LINE__, #cond); ++failures; } } while (0)
 
-static_assert(sizeof(lcm::PgoPose) == sizeof(lcm_pgo_pose) && sizeof(lcm_pgo_pose) == 96, "pose");
+static_assert(sizeof(lcm::Pose) == sizeof(lcm_pgo_pose) && sizeof(lcm_pgo_pose) == 96, "pose");
 static_assert(sizeof(lcm::PgoEdge) == sizeof(lcm_pgo_edge) && sizeof(lcm_pgo_edge) == 112, "edge");
 static_assert(sizeof(lcm_pgo_params) == 64 && sizeof(lcm_pgo_info) == 48 && offsetof(lcm::PgoState, done) == 48, "records");
 
@@ -148,39 +148,14 @@ static void check_params_and_values() {
     CHECK(lcm::pgo_inputs_problem(poses.data(), nullptr, 3, e.data(), 2, nullptr, &pl).code == LCM_OK && pl.n_int == 2);
 }
 
+// exp, log, the products and the 6 x 6 Cholesky: tests/cpp/geom_host_check.cpp
 static void check_arithmetic_and_host_calls() {
-    const double r[3] = {0.3, -0.2, 0.5};
-    double R[9], back[3];
-    lcm::pgo_exp(r, R);
-    CHECK(!lcm::pgo_rotation_problem(R) && lcm::pgo_log(R, back));
-    for (int k = 0; k < 3; ++k) CHECK(std::fabs(back[k] - r[k]) < 1e-15);
-    const double tiny[3] = {1e-17, 0, 0}, small[3] = {3e-6, -2e-6, 1e-6};
-    lcm::pgo_exp(tiny, R);
-    CHECK(std::memcmp(R, I3, sizeof(I3)) == 0);
-    lcm::pgo_exp(small, R);
-    CHECK(lcm::pgo_log(R, back) && back[0] != 0.0 && std::fabs(back[0] - 3e-6) < 1e-16);      // first order, not a zero vector
-    const double half[9] = {1, 0, 0, 0, -1, 0, 0, 0, -1};
-    CHECK(!lcm::pgo_log(half, back));
-    double a[21] = {4, 2, 5, 0, 1, 6, 0, 0, 1, 7, 0, 0, 0, 1, 8, 0, 0, 0, 0, 1, 9}, x[6] = {4, 7, 8, 9, 10, 10};
-    CHECK(lcm::pgo_chol6(a) && a[0] == 2.0 && a[1] == 1.0 && a[2] == 2.0);
-    lcm::pgo_lower_solve6(a, x);
-    lcm::pgo_upper_solve6(a, x);
-    const double full[6][6] = {{4, 2, 0, 0, 0, 0}, {2, 5, 1, 0, 0, 0}, {0, 1, 6, 1, 0, 0}, {0, 0, 1, 7, 1, 0}, {0, 0, 0, 1, 8, 1}, {0, 0, 0, 0, 1, 9}};
-    const double rhs[6] = {4, 7, 8, 9, 10, 10};
-    for (int i = 0; i < 6; ++i) {
-        double s = 0.0;
-        for (int j = 0; j < 6; ++j) s += full[i][j] * x[j];
-        CHECK(std::fabs(s - rhs[i]) < 1e-13);
-    }
-    double bad[21] = {1, 2, 1};                                     // not positive definite
-    CHECK(!lcm::pgo_chol6(bad));
-
     // the graph of :1441-1470 over four poses, pose 2 invalid; the drift and the linear correction of a known rotation
     std::vector<lcm_pgo_pose> poses(4);
     for (int i = 0; i < 4; ++i) {
         const double ri[3] = {0.0, 0.1 * i, 0.0};
         std::memset(&poses[i], 0, sizeof(poses[i]));
-        lcm::pgo_exp(ri, poses[i].R);
+        lcm::so3_exp(ri, poses[i].R);
         poses[i].t[0] = i; poses[i].t[2] = -2.0 * i;
     }
     const uint8_t valid[4] = {1, 1, 0, 1};
@@ -206,7 +181,7 @@ static void check_arithmetic_and_host_calls() {
     CHECK(std::memcmp(&fixed[0], &poses[0], 96) == 0 && std::memcmp(&fixed[2], &poses[2], 96) == 0);
     CHECK(std::fabs(lcm::pgo_rotation_drift(fixed.data(), 0, 3, I3)) < 1e-15);          // the whole error taken out at curr
     double r1[3];
-    CHECK(lcm::pgo_log(fixed[1].R, r1) && std::fabs(r1[1] - 0.0) < 1e-15);              // pose 1: 0.1 - 0.3 / 3
+    CHECK(lcm::so3_log(fixed[1].R, r1) && std::fabs(r1[1] - 0.0) < 1e-15);              // pose 1: 0.1 - 0.3 / 3
     CHECK(lcm::pgo_linear_correct(poses.data(), valid, 4, 0, 3, I3, poses.data()) && std::memcmp(poses.data(), fixed.data(), 4 * 96) == 0);
 }
 

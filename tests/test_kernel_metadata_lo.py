@@ -1,11 +1,14 @@
 """Code-object metadata of the RANSAC's local optimisation (lcm_lo.hip; hipcc cross-compiles gfx950 without a GPU): exactly
 the two kernels the file's header names, none with scratch memory or spills, each within the VGPR and LDS budget the header
-states, and the inlier rule, the projection and the constraint row called from lcm_epi_device.h, not restated."""
+states, the inlier rule, the projection and the constraint row called from lcm_epi_device.h, the packed index and the rotation's
+angle from lcm_geom_device.h, not restated."""
 import os
 import re
 import subprocess
 
 import pytest
+
+import geomsrc as G
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "slam-loop-closing_amd", "csrc")
@@ -66,4 +69,12 @@ def test_the_shared_rules_are_called_not_restated():
     assert dev.count("epi_put_row<1>(") == 1
     host = re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, "lcm_lo.cpp")).read())
     assert "epi_inlier(" not in host and "lo_eig9" not in host          # the host never restates or runs the model
+    # the eigenvector's packed index and the rotation's gate and angle are the shared header's; lo_eig9 keeps its LDS stride, its
+    # loops that are not unrolled and its loads before the gate
+    G.assert_defined_once_in_geom(("sym_index", "jacobi_angle"))
+    assert '#include "lcm_geom_device.h"' in dev and "zeta" not in dev and "1e-36" not in dev
+    eig = dev[dev.index("void lo_eig9("):dev.index("void lo_denormalise(")]
+    assert eig.count("jacobi_angle(") == 1 and set(re.findall(r"sym_index<(\w+)>", dev)) == {"9"} and "template <int STRIDE>" in dev
+    assert eig.count("#pragma clang loop unroll(disable)") == 3 and eig.count("* STRIDE]") == 18
+    assert eig.index("vq[k] = V[(9 * k + q) * STRIDE];") < eig.index("jacobi_angle(") < eig.index("W[sym_index<9>(k, p) * STRIDE] = cs * ap[k] - sn * aq[k];")
     assert "atomicAdd(" in src and not re.search(r"atomic\w*\([^)]*(double|float)", src)  # integer atomics only

@@ -1,12 +1,15 @@
 """Code-object metadata of the map building (lcm_map.hip; hipcc cross-compiles gfx950 without a GPU): exactly the kernels the file's
 header names, without scratch memory or spills, each within the VGPR and LDS budget the header states; and from the source text: the
-arithmetic defined once in lcm_map_device.h and called from the kernels, the Jacobi rotation not restated outside that header,
-every index of the 4 x 4 problem a compile-time constant, integer atomics only.  Metadata fields and source structure only."""
+arithmetic defined once in lcm_map_device.h and called from the kernels, the camera point, the projection, the packed index and
+the Jacobi rotation's angle taken from lcm_geom_device.h and stated nowhere else, every index of the 4 x 4 problem a compile-time
+constant, integer atomics only.  Metadata fields and source structure only."""
 import os
 import re
 import subprocess
 
 import pytest
+
+import geomsrc as G
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "slam-loop-closing_amd", "csrc")
@@ -56,7 +59,7 @@ def test_the_header_names_every_kernel_and_states_the_budget():
         assert all(BUDGET[n] == (vgprs, lds) for n in names)
     assert "in list order by construction" in flat and "the same call gives the same bytes" in flat and "radix select" in flat
     make = open(os.path.join(CSRC, "Makefile")).read()
-    assert all(f in make for f in ("lcm_map.hip", "lcm_map.cpp", "lcm_map_device.h", "lcm_map_host.h"))
+    assert all(f in make for f in ("lcm_map.hip", "lcm_map.cpp", "lcm_map_device.h", "lcm_map_host.h", G.GEOM))
 
 
 def test_the_arithmetic_exists_once_and_is_called_from_the_kernels():
@@ -66,25 +69,31 @@ def test_the_arithmetic_exists_once_and_is_called_from_the_kernels():
     cpp = open(os.path.join(CSRC, "lcm_map.cpp")).read()
     strip = lambda t: re.sub(r"//[^\n]*", "", t)                               # noqa: E731
     code, dev_code, host_code, cpp_code = strip(src), strip(dev), strip(host), strip(cpp)
-    for fn in ("double map_displacement(", "void map_system(", "void map_rotate_row(", "void map_rotate(", "void map_jacobi4(", "void map_camera_point(",
+    geom_code = strip(open(os.path.join(CSRC, G.GEOM)).read())
+    for fn in ("double map_displacement(", "void map_system(", "void map_rotate_row(", "void map_rotate(", "void map_jacobi4(",
                "double map_parallax_cos(", "double map_reproj_error(", "int map_record("):
-        assert dev.count(fn) == 1 and fn not in src and fn not in host and fn not in cpp, fn
-    assert re.findall(r'#include "([^"]+)"', src) == ["lcm_map_device.h"]
+        assert dev.count(fn) == 1 and fn not in src and fn not in host and fn not in cpp and fn not in geom_code, fn
+    # the shared functions are used, not restated: defined once in the shared header, in no other file of csrc
+    G.assert_defined_once_in_geom(("rigid_apply", "pinhole_project", "sym_index", "jacobi_angle"))
+    assert re.findall(r'#include "([^"]+)"', src) == ["lcm_map_device.h"] and '#include "lcm_geom_device.h"' in dev
+    assert dev_code.count("rigid_apply(") == 2 and dev_code.count("pinhole_project(") == 1 and dev_code.count("jacobi_angle(") == 1
     # the kernels call it: the record's arithmetic once, the displacement once
     assert code.count("map_record(") == 1 and code.count("map_displacement(") == 1
-    # the Jacobi rotation is stated in the device header alone: its angle formula appears nowhere else under csrc, the loop
-    # verification's own (the RANSAC's 3 x 3 and the local optimisation's 9 x 9) aside
+    # the Jacobi rotation's angle is stated in the shared header alone: its formula appears nowhere else under csrc, the
+    # RANSAC's 3 x 3 (compiled with contraction, so kept apart) aside
     for f in sorted(os.listdir(CSRC)):
         text = strip(open(os.path.join(CSRC, f)).read())
-        if f not in ("lcm_map_device.h", "lcm_lo_device.h", "lcm_epi_device.h"):
+        if f not in (G.GEOM, "lcm_epi_device.h"):
             assert "zeta" not in text, f
         if f != "lcm_map_device.h":
             assert "map_rotate" not in text and "map_jacobi4(" not in text and "map_system(" not in text, f
-    assert dev_code.count("zeta * zeta") == 1 and dev_code.count("map_jacobi4(") == 2 and dev_code.count("map_system(") == 2
+    assert geom_code.count("zeta * zeta") == 1 and dev_code.count("map_jacobi4(") == 2 and dev_code.count("map_system(") == 2
     # every index into M and the product is a compile-time constant: template arguments and literals, no subscript by a loop
     # variable inside the rotation, the six pairs unrolled, one loop over the sweeps
-    rot = dev_code[dev_code.index("void map_rotate_row("):dev_code.index("void map_camera_point(")]
-    assert set(re.findall(r"\bmap_sym\(([^()]*)\)", rot)) <= {"K, P", "K, Q", "P, P", "Q, Q", "P, Q", "0, 0", "1, 1", "2, 2", "3, 3"}
+    rot = dev_code[dev_code.index("void map_rotate_row("):dev_code.index("double map_parallax_cos(")]
+    assert set(re.findall(r"\bsym_index<4>\(([^()]*)\)", rot)) <= {"K, P", "K, Q", "P, P", "Q, Q", "P, Q", "0, 0", "1, 1", "2, 2", "3, 3"}
+    assert set(re.findall(r"\bsym_index<(\w+)>", dev_code)) == {"4"} and len(re.findall(r"\ba\[([^\]]*)\]", rot)) == len(re.findall(r"\ba\[sym_index<4>\(", rot))
+    assert "constexpr int sym_index(int i, int j)" in geom_code           # so that each of these is a constant
     assert set(re.findall(r"\bv\[([^\]]*)\]", rot)) <= {"4 * K + P", "4 * K + Q", "16"} | {str(i) for i in range(16)}
     assert [tuple(map(int, m)) for m in re.findall(r"map_rotate<(\d), (\d)>\(m, v\)", rot)] == [(0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3)]
     assert rot.count("for (") == 1 and "sweep < MAP_JACOBI_SWEEPS" in rot and "unroll(disable)" in rot

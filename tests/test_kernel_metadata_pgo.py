@@ -1,13 +1,15 @@
 """Code-object metadata of the pose-graph correction (lcm_pgo.hip; hipcc cross-compiles gfx950 without a GPU): exactly the
 kernels the file's header names, without scratch memory or spills, each within the VGPR and LDS budget the header states; and
-from the source text: exp, log, the edge residual and the 6 x 6 Cholesky defined once in lcm_pgo_device.h and called, not
-restated, by the kernels, no floating-point atomic, and the other kernel files' kernel lists as they were.  Metadata fields and
-source structure only."""
+from the source text: the edge residual defined once in lcm_pgo_device.h, exp, log, the products and the Cholesky once in
+lcm_geom_device.h, all called, not restated, by the kernels, no floating-point atomic, and the other kernel files' kernel lists as
+they were.  Metadata fields and source structure only."""
 import os
 import re
 import subprocess
 
 import pytest
+
+import geomsrc as G
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "slam-loop-closing_amd", "csrc")
@@ -59,31 +61,36 @@ def test_the_header_names_every_kernel_and_states_the_budget():
         assert f"{listed} {what}" in budget, (listed, what)
         assert all(BUDGET[n] == (vgprs, lds) for n in names)
     make = open(os.path.join(CSRC, "Makefile")).read()
-    assert "lcm_pgo.hip" in make and "lcm_pgo.cpp" in make and "lcm_pgo_device.h" in make and "lcm_pgo_host.h" in make
+    assert "lcm_pgo.hip" in make and "lcm_pgo.cpp" in make and "lcm_pgo_device.h" in make and "lcm_pgo_host.h" in make and G.GEOM in make
 
 
 def test_the_arithmetic_exists_once_and_is_called_from_the_kernels():
     src = open(os.path.join(CSRC, "lcm_pgo.hip")).read()
     dev = open(os.path.join(CSRC, "lcm_pgo_device.h")).read()
-    for fn in ("void pgo_exp(", "bool pgo_log(", "bool pgo_edge_residual(", "bool pgo_chol6(", "void pgo_lower_solve6(", "void pgo_upper_solve6("):
-        assert dev.count(fn) == 1 and fn not in src, fn
-    dev_code = re.sub(r"//[^\n]*", "", dev)
-    assert dev_code.count("atan2(") == 1 and dev_code.count("cos(theta)") == 1 and dev_code.count("sin(theta)") == 1
-    code = re.sub(r"//[^\n]*", "", src)                     # the kernels' text without its comments
+    geom = open(os.path.join(CSRC, G.GEOM)).read()
+    assert dev.count("bool pgo_edge_residual(") == 1 and "bool pgo_edge_residual(" not in src and "bool pgo_edge_residual(" not in geom
+    # the shared functions: defined once in the shared header, in no other file of csrc
+    G.assert_defined_once_in_geom(("so3_exp", "so3_log", "mat3_mul", "mat3_mul_tn", "mat3_apply", "chol", "lower_solve", "upper_solve", "tri_index"))
+    assert re.findall(r'#include "([^"]+)"', src) == ["lcm_pgo_device.h"] and '#include "lcm_geom_device.h"' in dev
+    dev_code, geom_code = G.strip(dev), G.strip(geom)
+    assert geom_code.count("atan2(") == 1 and geom_code.count("cos(theta)") == 1 and geom_code.count("sin(theta)") == 1
+    assert not set(re.findall(r"\b\w+\b", dev_code)) & {"atan2", "sin", "cos", "acos", "asin", "sincos", "theta"}
+    assert dev_code.count("mat3_mul(") == 1 and dev_code.count("mat3_mul_tn(") == 1 and dev_code.count("so3_log(") == 1 and dev_code.count("mat3_apply(") == 1
+    code = G.strip(src)                                     # the kernels' text without its comments
     assert code.count("pgo_edge_residual(") == 3            # the residual itself, +eps, -eps
-    assert code.count("pgo_exp(") == 2 and code.count("pgo_log(") == 1          # the poses' exp (linearise, write-back), the poses' log
-    assert code.count("pgo_chol6(") == 1 and code.count("pgo_lower_solve6(") == 2 and code.count("pgo_upper_solve6(") == 1
+    assert code.count("so3_exp(") == 2 and code.count("so3_log(") == 1          # the poses' exp (linearise, write-back), the poses' log
+    assert code.count("chol<6>(") == 1 and code.count("lower_solve<6>(") == 2 and code.count("upper_solve<6>(") == 1 and code.count("tri_index(") == 1
     # no trigonometry, no square root of a pivot block and no rotation formula of the kernel file's own
     words = set(re.findall(r"\b\w+\b", code))
     assert not words & {"atan2", "sin", "cos", "acos", "asin", "sincos", "theta"}
     # no floating-point atomics: no atomic at all
-    assert not re.search(r"atomic", code, flags=re.I) and not re.search(r"atomic", dev, flags=re.I)
+    assert not re.search(r"atomic", code, flags=re.I) and not re.search(r"atomic", dev, flags=re.I) and not re.search(r"atomic", geom, flags=re.I)
     assert "asm" not in words and "__builtin_amdgcn_global_atomic_fadd_f64" not in code
     # the host runs none of it but through lcm_pgo_host.h's host-only calls
     host = re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, "lcm_pgo.cpp")).read())
-    for fn in ("pgo_exp(", "pgo_log(", "pgo_edge_residual(", "pgo_chol6("):
+    for fn in ("so3_exp(", "so3_log(", "pgo_edge_residual(", "chol<"):
         assert fn not in host, fn
-    assert "#pragma clang fp contract(off)" in dev and "fp contract(off)" in src
+    assert "#pragma clang fp contract(off)" in dev and "fp contract(off)" in src and "#pragma clang fp contract(off)" in geom
 
 
 def test_the_other_kernel_files_keep_their_kernels():
