@@ -197,6 +197,28 @@ def triangulate(plan, pts, mask=None, pp=None, sweeps=JACOBI_SWEEPS, h=None):
     return r
 
 
+def status_of_fields(tri, baseline, cosine, pp=None):
+    """map_record's five lines over the FIELDS of a lcm_map_tri array (the device's or Records.tri()): depth1 or depth2 <= 0;
+    rel = depth1 / baseline (the same IEEE double division as on the device) against both depth limits; cos_parallax > cos_min;
+    either error > max_reproj; else accepted.  Nothing is recomputed, so the rule holds on every record with a point whatever
+    its distance from a threshold.  uint8 [n]; meaningless where the record has no point (its fields are all zero)."""
+    pp = params(pp)
+    t = np.asarray(tri)
+    d1, d2 = t["depth1"].astype(np.float64), t["depth2"].astype(np.float64)
+    with np.errstate(all="ignore"):
+        rel = d1 / np.float64(baseline)
+        depth = (d1 <= 0) | (d2 <= 0) | (rel < np.float64(pp["min_depth"])) | (rel > np.float64(pp["max_depth"]))
+    par = t["cos_parallax"] > np.float64(cosine)
+    rep = (t["err1"] > np.float64(pp["max_reproj"])) | (t["err2"] > np.float64(pp["max_reproj"]))
+    return np.where(depth, REJ_DEPTH, np.where(par, REJ_PARALLAX, np.where(rep, REJ_REPROJ, ACCEPTED))).astype(np.uint8)
+
+
+def rel_depth(tri, baseline):
+    """rel = depth1 / baseline of every record, the division the device makes."""
+    with np.errstate(all="ignore"):
+        return np.asarray(tri)["depth1"].astype(np.float64) / np.float64(baseline)
+
+
 # ---- the merge ---------------------------------------------------------------------------------------------------------------
 def merge_sequential(matches, pts, tri, status, kf1, kf2, table1, table2, n_points):
     """src/main.cpp:1315-1340 as the reference walks it, one accepted record after another.  matches int [n, 2] (query_idx,
