@@ -1021,6 +1021,116 @@ LCM_API int  lcm_map_db_track(lcm_handle* h, int last_slot, int curr_slot, doubl
                               int n_points, const lcm_map_params* mp, lcm_ba_point* points_out, int cap_points, lcm_ba_obs* obs_out,
                               int cap_obs, uint8_t* status_out, lcm_map_keyframe_report* report);
 
+/* ---- the front end: SIFT keypoints (scale space, extrema, refinement) ------------------------------------------ */
+/* The first half of detectAndDescribeSIFT (src/main.cpp:497-504, called on every frame at :1119 and :1150) on the device: the
+ * Gaussian scale space, the difference-of-Gaussians (DoG) layers, the 26-neighbour extrema and the sub-pixel refinement with its
+ * contrast and edge tests (lcm_sift_device.h, lcm_sift_host.h, lcm_sift.hip).  The pyramid stays on the device in a
+ * lcm_sift_space for the stage that follows.  NOT here, and still the caller's: cv::undistort, the orientation histogram, the
+ * 128-D descriptor, retainBest(4000) and the removal of duplicate keypoints; no batches of images, no group form.
+ * The contract is the definition below, restated in numpy by tests/siftref.py and held bit for bit.  It is modelled on OpenCV's
+ * sift.dispatch.cpp, but parity with cv::SIFT is unpinned: OpenCV is not available to compare with, its blur runs through
+ * vectorised filter engines whose summation order is not this one, and its exp / pow are the platform's.
+ * All image arithmetic is float32, every product and every sum rounded on its own (no contraction), sums in the stated order.
+ *   plan        (host, double; lcm_sift_plan) base = (2 w, 2 h) with upsample, else (w, h); n_octaves = cvRound(log2(min(base_w,
+ *               base_h)) - 2) + (upsample ? 1 : 0) unless given (cvRound rounds half to even); octave o has (base_w >> o, base_h >> o)
+ *               pixels, n_octave_layers + 3 Gaussian and n_octave_layers + 2 DoG layers.  sig[0] = sigma; sig[i] = sqrt(total^2 -
+ *               prev^2), prev = sigma k^(i-1), total = prev k, k = 2^(1 / n_octave_layers).  The first blur's sigma is
+ *               sqrt(max(sigma^2 - a^2, 0.01)), a = 2 init_sigma with upsample, else init_sigma.  Taps of a sigma: radius r =
+ *               (cvRound(8 sig + 1) | 1) / 2, exp(-(j - r)^2 / (2 sig^2)) for j = 0 .. 2 r in double, divided by their sum taken in
+ *               ascending j, then rounded to float.
+ *   base image  uint8 -> float; with upsample the 2x bilinear enlargement: source coordinate (d + 0.5) / 2 - 0.5, clamped to the
+ *               image, weights 0.25 and 0.75 (exact); then one blur with the first blur's taps gives layer 0 of octave 0.
+ *   blur        tmp[y][x] = sum_j t[j] src[y][m(x + j - r)], dst[y][x] = sum_j t[j] tmp[m(y + j - r)][x]; j ascends from 0 and the
+ *               sum starts from the first product; m is the reflect-101 index, folded with period 2 (n - 1) until it is inside
+ *               (0 for n == 1).  Layer i of an octave is the blur of layer i - 1 with the taps of sig[i].
+ *   octaves     layer 0 of octave o + 1 is layer n_octave_layers of octave o at the pixels (2 x, 2 y).  D[l] = G[l + 1] - G[l].
+ *   extrema     T = floor(0.5 contrast_threshold / n_octave_layers 255) (double).  At layers 1 .. n_octave_layers and border <= x <
+ *               cols - border, border <= y < rows - border: |v| > T and (v > 0 and v >= all 26 neighbours, or v < 0 and v <= all
+ *               26).  Candidates come in ascending (octave, layer, row, col) order, by an ordered compaction (block counts, an
+ *               exclusive scan, a ballot rank): no atomic cursor, the same bytes every time.
+ *   refinement  one candidate at a time, at most max_steps steps.  With s = (float) 1 / 255 (the rounded quotient), at (layer, row,
+ *               col): dD = ((D[c+1] - D[c-1]) (0.5 s), (D[r+1] - D[r-1]) (0.5 s), (next - prev) (0.5 s)); dxx = ((D[c+1] + D[c-1]) -
+ *               2 v) s, dyy and dss likewise; dxy = (((D[r+1][c+1] - D[r+1][c-1]) - D[r-1][c+1]) + D[r-1][c-1]) (0.25 s), dxs and
+ *               dys likewise over (next, prev).  X = -(H^-1 dD) by 3 x 3 Gaussian elimination with partial pivoting (the largest
+ *               |.|, the first of equals; f = a_ik / a_kk, a_ij - f a_kj; back substitution from the last row, each row's products
+ *               subtracted left to right); a zero pivot rejects.  All |X_i| < 0.5: converged.  Else rejected when an |X_i| >
+ *               INT_MAX / 3 (715827882 as a float; a NaN too); else (col, row, layer) += rint(X) (half to even) and rejected when
+ *               that leaves layers 1 .. n_octave_layers or the border; rejected when the last step did not converge.  Then contr =
+ *               v s + ((dD0 Xc + dD1 Xr) + dD2 Xs) 0.5, rejected when |contr| n_octave_layers < (float) contrast_threshold; tr =
+ *               dxx + dyy, det = dxx dyy - dxy dxy at the last position, rejected when det <= 0 or (tr tr) e >= ((e + 1)(e + 1)) det
+ *               with e = (float) edge_threshold.  A survivor's record: x = (col + Xc) 2^o and y = (row + Xr) 2^o, halved with
+ *               upsample; size = ((float) sigma P(e)) (2^o 2), halved with upsample, where e = (layer + Xs) / n_octave_layers and
+ *               P(e) = 2^rint(e) p((e - rint(e)) 0.693147182f), p the Taylor polynomial of exp to the 8th power by Horner with the
+ *               coefficients (float)(1 / k!) (only + and x, so that every implementation gives the same bits; within 2 float ulp of
+ *               2^e); response = |contr|; xi = Xs; octave, layer, col, row the last position.  Survivors keep candidate order.
+ * Limits: an input of 1 .. LCM_SIFT_MAX_SIDE pixels a side, at most LCM_SIFT_MAX_OCTAVES octaves, every radius at most
+ * LCM_SIFT_MAX_RADIUS (the defaults need 13; sigma 1.6 with n_octave_layers 1 needs 45), the smallest octave at least one pixel:
+ * LCM_ERR_CAPACITY above the limits, LCM_ERR_INVALID_ARG for a size that gives no octave.  A space holds room for min(every pixel
+ * that may be a candidate, LCM_SIFT_MAX_CANDIDATES) candidates; a search that finds more is LCM_ERR_CAPACITY. */
+#define LCM_SIFT_MAX_SIDE 4096
+#define LCM_SIFT_MAX_OCTAVES 16
+#define LCM_SIFT_MAX_RADIUS 48
+#define LCM_SIFT_MAX_CANDIDATES 1048576
+typedef enum lcm_sift_kind { LCM_SIFT_GAUSSIAN = 0, LCM_SIFT_DOG = 1 } lcm_sift_kind;
+typedef struct lcm_sift_params {      /* defaults = cv::SIFT::create's and OpenCV's constants */
+    double  contrast_threshold;       /* 0.04 */
+    double  edge_threshold;           /* 10 */
+    double  sigma;                    /* 1.6 */
+    double  init_sigma;               /* 0.5: the blur the input is taken to have (SIFT_INIT_SIGMA) */
+    int32_t n_octave_layers;          /* 3; 1 .. 8 */
+    int32_t upsample;                 /* 1: the first octave is the image enlarged 2x (firstOctave -1); 0 or 1 */
+    int32_t n_octaves;                /* 0: derived from the size; else 1 .. LCM_SIFT_MAX_OCTAVES */
+    int32_t border;                   /* 5 (SIFT_IMG_BORDER); >= 1 */
+    int32_t max_steps;                /* 5 (SIFT_MAX_INTERP_STEPS); >= 1 */
+    int32_t reserved[3];              /* 0 */
+} lcm_sift_params;                    /* 64 bytes */
+typedef struct lcm_sift_plan_info {
+    int32_t  n_octaves, n_gauss, n_dog, base_w, base_h, first_radius, max_radius, reserved;
+    int32_t  width[16], height[16];   /* per octave */
+    int32_t  radius[12];              /* per Gaussian layer; radius[0] = 0 (layer 0 is not blurred from a layer) */
+    double   first_sigma, sig[12];
+    uint64_t space_floats;            /* floats of a space of this plan: the base image, then per octave its Gaussian and DoG layers */
+} lcm_sift_plan_info;                 /* 320 bytes */
+typedef struct lcm_sift_keypoint { float x, y, size, response, xi; int16_t octave, layer; int32_t col, row; } lcm_sift_keypoint;   /* 32 bytes */
+typedef struct lcm_sift_candidate { int32_t octave, layer, row, col; } lcm_sift_candidate;                                          /* 16 bytes */
+typedef struct lcm_sift_space lcm_sift_space;
+typedef struct lcm_sift_space_info_t {
+    int32_t  max_w, max_h, w, h;      /* what the space was created for; the last build's image (0, 0: none yet) */
+    uint64_t device_bytes;            /* everything the space holds on the device, allocated at creation */
+    uint64_t candidate_capacity;
+    lcm_sift_plan_info plan;          /* the last build's (zero before the first) */
+} lcm_sift_space_info_t;
+LCM_API void lcm_sift_params_default(lcm_sift_params* p);
+/* Host only, pure, no device needed.  A bad parameter (non-finite or non-positive thresholds and sigmas, n_octave_layers outside
+ * 1 .. 8, border < 1, max_steps < 1, n_octaves outside 0 .. 16, upsample not 0 or 1) is LCM_ERR_INVALID_ARG; the limits above.
+ * lcm_sift_plan_read: the taps of Gaussian layer `layer` (1 .. n_octave_layers + 2; -1: the first blur), 2 radius + 1 of them;
+ * cap too small: LCM_ERR_CAPACITY, *n_taps set, nothing written. */
+LCM_API int  lcm_sift_plan(int w, int h, const lcm_sift_params* sp, lcm_sift_plan_info* out);
+LCM_API int  lcm_sift_plan_read(int w, int h, const lcm_sift_params* sp, int layer, float* taps, int cap, int* n_taps);
+/* A scale space for images of up to max_w x max_h under *sp (NULL: the defaults).  All device memory is allocated here, once:
+ * the pyramid of the largest image, the image, the taps, the block counts and the candidates' room.  The parameters and the size
+ * are checked on the host before the handle is looked at (then LCM_ERR_NO_DEVICE without a device).  Destroy a space before its handle. */
+LCM_API int  lcm_sift_space_create(lcm_handle* h, int max_w, int max_h, const lcm_sift_params* sp, lcm_sift_space** out);
+LCM_API void lcm_sift_space_destroy(lcm_sift_space* s);
+/* Uploads the gray image (h rows of w bytes, `stride` bytes apart, stride >= w) and builds the pyramid, everything on the handle's
+ * stream; finished on return.  A smaller image than the last one reuses the same memory under its own plan. */
+LCM_API int  lcm_sift_space_build(lcm_sift_space* s, const uint8_t* img, int w, int h, size_t stride);
+LCM_API int  lcm_sift_space_info(const lcm_sift_space* s, lcm_sift_space_info_t* out);
+/* One layer of the last build (kind: lcm_sift_kind; octave 0 .. n_octaves - 1; layer 0 .. n_octave_layers + 2, or + 1 for a DoG layer)
+ * to or from width[octave] x height[octave] packed floats.  The write form is the door through which tests plant exact DoG values:
+ * it changes that layer alone and invalidates nothing else (a DoG layer no longer is the difference of its Gaussians, nor a later
+ * Gaussian the blur of a written one) until the next build. */
+LCM_API int  lcm_sift_space_read(lcm_sift_space* s, int kind, int octave, int layer, float* out);
+LCM_API int  lcm_sift_space_write(lcm_sift_space* s, int kind, int octave, int layer, const float* in);
+/* The raw candidates of the built space, in order.  *n = their number; more than cap: LCM_ERR_CAPACITY, nothing written to cand. */
+LCM_API int  lcm_sift_extrema(lcm_sift_space* s, lcm_sift_candidate* cand, size_t cap, size_t* n);
+/* Extrema, refinement and compaction: only the two counts come back before the records do.  *n = the survivors, *n_candidates
+ * (optional) = the candidates; more survivors than cap: LCM_ERR_CAPACITY with both counts set and nothing else written. */
+LCM_API int  lcm_sift_detect(lcm_sift_space* s, lcm_sift_keypoint* kp, size_t cap, size_t* n, size_t* n_candidates);
+/* Build + detect in one call on a space cached in the handle (made anew when *sp changes or the image outgrows it). */
+LCM_API int  lcm_sift_detect_image(lcm_handle* h, const uint8_t* img, int w, int height, size_t stride, const lcm_sift_params* sp,
+                                   lcm_sift_keypoint* kp, size_t cap, size_t* n);
+
 /* ---- loop search against the stored database --------------------------------------------------------- */
 /* Score `query` (id query_frame_id) against every stored frame with query_frame_id - id >= min_gap, ascending
  * slot order.  out_scores / out_frame_ids need room for lcm_db_size() records. */

@@ -157,6 +157,31 @@ MAP_MAX_PAIRS, MAP_MAX_RECORDS = 4096, 1 << 24
 _MAP_FIELDS = tuple(f[0] for f in MapParams._fields_[:-1])
 
 
+class SiftParams(C.Structure):
+    """lcm_sift_params: the detector's thresholds and sigmas, the layers per octave, the first octave, the border, the steps (64 bytes)."""
+    _fields_ = [("contrast_threshold", C.c_double), ("edge_threshold", C.c_double), ("sigma", C.c_double), ("init_sigma", C.c_double),
+                ("n_octave_layers", C.c_int32), ("upsample", C.c_int32), ("n_octaves", C.c_int32), ("border", C.c_int32), ("max_steps", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+class SiftPlanInfo(C.Structure):
+    """lcm_sift_plan_info: a scale space's octaves, sizes, sigmas and radii (320 bytes)."""
+    _fields_ = [("n_octaves", C.c_int32), ("n_gauss", C.c_int32), ("n_dog", C.c_int32), ("base_w", C.c_int32), ("base_h", C.c_int32),
+                ("first_radius", C.c_int32), ("max_radius", C.c_int32), ("reserved", C.c_int32), ("width", C.c_int32 * 16), ("height", C.c_int32 * 16),
+                ("radius", C.c_int32 * 12), ("first_sigma", C.c_double), ("sig", C.c_double * 12), ("space_floats", C.c_uint64)]
+
+
+class SiftSpaceInfo(C.Structure):
+    """lcm_sift_space_info_t: what a space was made for, its last image, its device bytes and candidate room, the last build's plan."""
+    _fields_ = [("max_w", C.c_int32), ("max_h", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("device_bytes", C.c_uint64),
+                ("candidate_capacity", C.c_uint64), ("plan", SiftPlanInfo)]
+
+
+SIFT_GAUSSIAN, SIFT_DOG = 0, 1                                                    # lcm_sift_kind
+SIFT_MAX_SIDE, SIFT_MAX_OCTAVES, SIFT_MAX_RADIUS, SIFT_MAX_CANDIDATES = 4096, 16, 48, 1 << 20
+_SIFT_FIELDS = tuple(f[0] for f in SiftParams._fields_[:-1])
+
+
 class LoParams(C.Structure):
     """lcm_lo_params: the rounds of the RANSAC's local optimisation and their threshold multipliers (96 bytes)."""
     _fields_ = [("rounds", C.c_int32), ("seeds", C.c_int32), ("mult", C.c_double * 8), ("reserved", C.c_uint32 * 6)]
@@ -224,6 +249,10 @@ MAP_TRI_DTYPE = np.dtype([("X", "<f8", (3,)), ("depth1", "<f8"), ("depth2", "<f8
                           ("err2", "<f8")])                                    # lcm_map_tri
 MAP_PAIR_INFO_DTYPE = np.dtype([("baseline", "<f8"), ("cos_min", "<f8"), ("counts", "<i4", (8,))])      # lcm_map_pair_info
 assert MAP_TRI_DTYPE.itemsize == 64 and MAP_PAIR_INFO_DTYPE.itemsize == 48 and C.sizeof(MapParams) == 112 and C.sizeof(MapKeyframeReport) == 168
+SIFT_KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("response", "<f4"), ("xi", "<f4"), ("octave", "<i2"),
+                                ("layer", "<i2"), ("col", "<i4"), ("row", "<i4")])                        # lcm_sift_keypoint
+SIFT_CANDIDATE_DTYPE = np.dtype([("octave", "<i4"), ("layer", "<i4"), ("row", "<i4"), ("col", "<i4")])     # lcm_sift_candidate
+assert SIFT_KEYPOINT_DTYPE.itemsize == 32 and SIFT_CANDIDATE_DTYPE.itemsize == 16 and C.sizeof(SiftParams) == 64 and C.sizeof(SiftPlanInfo) == 320
 LO_INFO_DTYPE = np.dtype([("seed_iter", "<i4"), ("round", "<i4"), ("n_inliers_ransac", "<i4"), ("status", "<i4")])    # lcm_lo_info
 assert LO_INFO_DTYPE.itemsize == C.sizeof(LoInfo) == 16 and C.sizeof(LoParams) == 96
 assert SCORE_DTYPE.itemsize == C.sizeof(Score) == 8
@@ -357,6 +386,18 @@ _SIGNATURES = {
     "lcm_map_db_track": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.POINTER(EpiParams), C.POINTER(LoParams), C.POINTER(PoseParams), _vp, _vp,
                                     _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.POINTER(MapParams),
                                     _vp, C.c_int, _vp, C.c_int, _vp, C.POINTER(MapKeyframeReport)]),
+    "lcm_sift_params_default": (None, [C.POINTER(SiftParams)]),
+    "lcm_sift_plan": (C.c_int, [C.c_int, C.c_int, C.POINTER(SiftParams), C.POINTER(SiftPlanInfo)]),
+    "lcm_sift_plan_read": (C.c_int, [C.c_int, C.c_int, C.POINTER(SiftParams), C.c_int, _vp, C.c_int, C.POINTER(C.c_int)]),
+    "lcm_sift_space_create": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(SiftParams), C.POINTER(_vp)]),
+    "lcm_sift_space_destroy": (None, [_vp]),
+    "lcm_sift_space_build": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_size_t]),
+    "lcm_sift_space_info": (C.c_int, [_vp, C.POINTER(SiftSpaceInfo)]),
+    "lcm_sift_space_read": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp]),
+    "lcm_sift_space_write": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp]),
+    "lcm_sift_extrema": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "lcm_sift_detect": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "lcm_sift_detect_image": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_size_t, C.POINTER(SiftParams), _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "lcm_query_scores": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _i32p]),
     "lcm_query_submit": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _i32p]),
     "lcm_query_collect": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i32p]),
@@ -692,6 +733,41 @@ def default_map_params(**over) -> MapParams:
             raise TypeError(f"lcm_map_params has no field {k!r}")
         setattr(p, k, v)
     return p
+
+
+def default_sift_params(**over) -> SiftParams:
+    """lcm_sift_params_default (contrast 0.04, edge 10, sigma 1.6, init_sigma 0.5, 3 layers, upsample, derived octaves, border 5, 5 steps),
+    then the given fields."""
+    p = SiftParams()
+    load_library().lcm_sift_params_default(C.byref(p))
+    for k, v in over.items():
+        if k not in _SIFT_FIELDS:
+            raise TypeError(f"lcm_sift_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def sift_plan(w: int, h: int, sp: Optional[SiftParams] = None) -> SiftPlanInfo:
+    """lcm_sift_plan: host only, no device needed."""
+    out = SiftPlanInfo()
+    _check(load_library().lcm_sift_plan(w, h, _ref(sp), C.byref(out)))
+    return out
+
+
+def sift_plan_taps(w: int, h: int, layer: int, sp: Optional[SiftParams] = None) -> np.ndarray:
+    """lcm_sift_plan_read: the float taps of Gaussian layer `layer` (-1: the first blur)."""
+    taps, n = np.zeros(2 * SIFT_MAX_RADIUS + 1, np.float32), C.c_int(0)
+    _check(load_library().lcm_sift_plan_read(w, h, _ref(sp), layer, _ptr(taps), len(taps), C.byref(n)))
+    return taps[:n.value].copy()
+
+
+def _gray(img) -> np.ndarray:
+    """A uint8 gray image whose rows are contiguous (a row stride above the width is kept)."""
+    a = np.asarray(img)
+    if a.dtype != np.uint8 or a.ndim != 2 or a.strides[1] != 1 or a.strides[0] < a.shape[1]:
+        a = np.ascontiguousarray(a, np.uint8)
+    assert a.ndim == 2
+    return a
 
 
 def _point_pairs(pts) -> np.ndarray:
@@ -1622,6 +1698,19 @@ class Matcher:
         lists = dict(results=res, pose_results=pres, info=info, out=out[:n], pts=pts[:n], mask=mask[:n], pose_mask=pmask[:n], offsets=offs)
         return lists, rep, points[:rep.n_new], obs[:2 * rep.n_new + rep.n_merged], status[:n]
 
+    # -- the front end: SIFT keypoints (lcm_sift_*) --
+    def sift_space(self, max_w: int, max_h: int, sp: Optional[SiftParams] = None) -> "SiftSpace":
+        """lcm_sift_space_create: a scale space for images of up to max_w x max_h; close it before the matcher."""
+        return SiftSpace(self, max_w, max_h, sp)
+
+    def sift_detect_image(self, img, sp: Optional[SiftParams] = None, cap: int = 1 << 16) -> np.ndarray:
+        """lcm_sift_detect_image: SIFT_KEYPOINT_DTYPE[n] of a uint8 gray image, on a space cached in the handle."""
+        a = _gray(img)
+        kp, n = np.zeros(max(cap, 1), SIFT_KEYPOINT_DTYPE), C.c_size_t(0)
+        _check(self._lib.lcm_sift_detect_image(self._h, a.ctypes.data_as(_vp), a.shape[1], a.shape[0], a.strides[0], _ref(sp), _ptr(kp), cap,
+                                               C.byref(n)))
+        return kp[:n.value]
+
     def query_scores(self, query, query_frame_id: int) -> Tuple[np.ndarray, np.ndarray]:
         q = _rows(query)
         cap = max(len(self), 1)
@@ -1874,6 +1963,63 @@ class Matcher:
     def dev_download(self, d_ptr: int, out: np.ndarray):
         assert out.flags["C_CONTIGUOUS"]
         _check(self._lib.lcm_dev_download(self._h, out.ctypes.data_as(_vp), _vp(d_ptr), out.nbytes))
+
+
+class SiftSpace:
+    """A lcm_sift_space: the Gaussian and DoG pyramid of one image at a time, on the device."""
+
+    def __init__(self, matcher: Matcher, max_w: int, max_h: int, sp: Optional[SiftParams] = None):
+        self._lib, self._m, self._s = matcher._lib, matcher, _vp()
+        _check(self._lib.lcm_sift_space_create(matcher._h, max_w, max_h, _ref(sp), C.byref(self._s)))
+
+    def close(self):
+        if self._s:
+            self._lib.lcm_sift_space_destroy(self._s)
+            self._s = _vp()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def build(self, img):
+        a = _gray(img)
+        _check(self._lib.lcm_sift_space_build(self._s, a.ctypes.data_as(_vp), a.shape[1], a.shape[0], a.strides[0]))
+
+    def info(self) -> SiftSpaceInfo:
+        out = SiftSpaceInfo()
+        _check(self._lib.lcm_sift_space_info(self._s, C.byref(out)))
+        return out
+
+    def read(self, kind: int, octave: int, layer: int) -> np.ndarray:
+        pl = self.info().plan
+        if not 0 <= octave < max(pl.n_octaves, 1):
+            raise LcmError(-1, "no such octave")
+        out = np.zeros((pl.height[octave], pl.width[octave]), np.float32)
+        _check(self._lib.lcm_sift_space_read(self._s, kind, octave, layer, _ptr(out)))
+        return out
+
+    def write(self, kind: int, octave: int, layer: int, values):
+        pl = self.info().plan
+        a = np.ascontiguousarray(values, np.float32)
+        assert 0 <= octave < pl.n_octaves and a.shape == (pl.height[octave], pl.width[octave])
+        _check(self._lib.lcm_sift_space_write(self._s, kind, octave, layer, _ptr(a)))
+
+    def extrema(self, cap: Optional[int] = None, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """lcm_sift_extrema: SIFT_CANDIDATE_DTYPE[n], in (octave, layer, row, col) order."""
+        cap = int(self.info().candidate_capacity) if cap is None else cap
+        out, n = np.zeros(max(cap, 1), SIFT_CANDIDATE_DTYPE) if out is None else out, C.c_size_t(0)
+        _check(self._lib.lcm_sift_extrema(self._s, _ptr(out), cap, C.byref(n)))
+        return out[:n.value]
+
+    def detect(self, cap: Optional[int] = None, out: Optional[np.ndarray] = None) -> Tuple[np.ndarray, int]:
+        """lcm_sift_detect: (SIFT_KEYPOINT_DTYPE[n], the candidates' number)."""
+        cap = int(self.info().candidate_capacity) if cap is None else cap
+        kp = np.zeros(max(cap, 1), SIFT_KEYPOINT_DTYPE) if out is None else out
+        n, nc = C.c_size_t(0), C.c_size_t(0)
+        _check(self._lib.lcm_sift_detect(self._s, _ptr(kp), cap, C.byref(n), C.byref(nc)))
+        return kp[:n.value], nc.value
 
 
 def merge_shard_scores_host(shard_scores: Sequence[np.ndarray], ids, min_gap: int) -> Tuple[np.ndarray, np.ndarray]:

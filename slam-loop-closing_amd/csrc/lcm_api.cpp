@@ -216,6 +216,7 @@ void lcm_destroy(lcm_handle* h) {
     if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
     if (h->stream2) (void)hipStreamSynchronize(h->stream2);
     for (QuerySlot& q : h->qslots) if (q.stream) (void)hipStreamSynchronize(q.stream);
+    lcm::sift_cached_destroy(h);
     (void)hipFree(h->d_rows); (void)hipFree(h->d_counts);
     (void)hipFree(h->d_keys); (void)hipFree(h->plan.d_items); (void)hipFree(h->plan.d_pk_tab);
     (void)hipFree(h->d_bulk_scores); (void)hipFree(h->d_meta); (void)hipFree(h->d_cands);

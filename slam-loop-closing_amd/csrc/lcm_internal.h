@@ -14,6 +14,7 @@
 //   lcm_pgo.cpp        pose-graph Gauss-Newton correction of the closed loop (lcm_pgo_*)
 //   lcm_ba.cpp         alternating bundle adjustment and outlier removal after the loop (lcm_ba_*)
 //   lcm_map.cpp        the map before the loop: keyframe gates, triangulation, filters and merge (lcm_map_*)
+//   lcm_sift.cpp       the front end: SIFT scale space, extrema and refinement (lcm_sift_*)
 //   lcm_verify.cpp     the three as one staged pipeline over a VerifyPlan (lcm_verify_host.h); the store's and the host-list forms
 // Not installed; the public surface is include/lcm.h.
 #pragma once
@@ -331,6 +332,7 @@ struct lcm_handle {
         lcm::Observation* d_obs = nullptr;      size_t d_obs_n = 0;
         uint8_t* d_status_out = nullptr;   size_t d_status_out_n = 0;
     } map;
+    lcm_sift_space* sift_cached = nullptr;      // lcm_sift_detect_image's space (lcm_sift.cpp), made at its first call
     lcm_launch_info info{};
     bool info_pending = false;
 };
@@ -569,6 +571,8 @@ int map_track_stages(lcm_handle* h, const MapTrack& t, const uint4* d_pts, const
                      uint32_t* launches);
 int map_keyframe_stages(lcm_handle* h, const MapTrack& t, const uint4* d_pts, const uint64_t* d_off, const uint4* d_matches,
                         const uint8_t* d_pose_mask, uint32_t n, const lcm_pose_result& pr, uint32_t* launches);
+// ---- lcm_sift.cpp: the space that lcm_sift_detect_image cached in the handle, freed (lcm_destroy)
+void sift_cached_destroy(lcm_handle* h);
 }  // namespace lcm
 
 namespace {
